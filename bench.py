@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mvoxel-channels/s of the voxel-descriptor hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1..cfg5|dist|dropin] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1..cfg5|dist|dropin] [--batch B] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (bin -> scan -> fill -> tile kernel, all on the GPU) over one
 batch of synthetic items that is ALREADY resident in HBM; features stay resident in HBM (float32
@@ -12,7 +12,7 @@ N > 1: one process per GPU over RCCL.  Started by the driver under torch.distrib
 invoked as plain `python bench.py --gpus N` -- this file starts the N ranks itself (launch_ranks) and
 fails loudly when the node has fewer devices.  The batch of N x B items is sharded with
 moleculekit_amd.distributed.ShardedVoxelizer: every rank generates, stages (pinned memory) and keeps only
-its own B items (weak scaling), and the timed region holds no collective.  The trivial gather of the
+its own B items (weak scaling), and the timed region holds no collective.  With --full the trivial gather of the
 feature tensors is timed separately: `gather_ms` (one padded all-gather after the compute) and
 `gather_overlapped_extra_ms` (chunks gathered on a communication stream while the next chunk is computed).
 The headline workload is the same at every N (the driver divides the per-N values); north_star's "batched
@@ -21,12 +21,19 @@ molecules" case (cfg3) runs through the same sharded path as a secondary leg (`b
 MKAMD_BENCH_SHARE_DEVICES=1 rehearses the real multi-process path on a box with fewer GPUs than ranks (ranks share
 devices; the line carries `config.rehearsal` and is not a scaling measurement).
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events recorded around the tile
-kernel on the stream it runs on; at N = 1 `other_workloads` carries the same measurement for the other
-BASELINE configs; `cpu_baseline` times the oracle (oracle/liboracle.so, a port of the reference's serial
-Cython kernel) on a bounded sample of the same workload on 1 host core.  Before the W warm-up steps the workload runs
-untimed for `--settle-seconds` (clocks; `config.clock_settle_s`); `sustained` repeats the steps for seconds and
-reports the shader clock the device held meanwhile.  stdout carries the JSON line only.
+Prints ONE JSON line (rank 0).  Before the W warm-up steps the workload runs untimed for `--settle-seconds`
+(clocks; `config.clock_settle_s`).  A plain run stops there: set-up, warm-up, the K timed steps, the outputs
+(`--dump-outputs DIR`) and the headline line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`,
+`config`).  Everything else is measured with `--full`: `roofline`, measured live with HIP events recorded
+around the tile kernel on the stream it runs on; at N = 1 `other_workloads`, the same measurement for the other
+BASELINE configs; `cpu_baseline`, the oracle (oracle/liboracle.so, a port of the reference's serial Cython
+kernel) timed on a bounded sample of the same workload on 1 host core; `sustained`, the steps repeated for
+seconds with the shader clock the device held meanwhile; the single-grid and drop-in latency probes; at N > 1 the
+feature gathers.  The timed steps are the same in both modes.  stdout carries the JSON line only.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last step -- the float32 [B, V, C]
+feature tensor of rank 0's items -- as DIR/*.npy (dump_outputs); the inputs are seeded, so two builds can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -367,6 +374,30 @@ def run_workload(name, B, steps, warmup, ctx, dev, rank, world, args, fence, wan
     return res
 
 
+DUMP_WHOLE_BYTES = 48 << 20      # --dump-outputs: a feature tensor up to this size is written whole, a larger one sampled
+DUMP_SAMPLE = 1 << 22            # voxel-channels in the sample (16 MiB of float32)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out, folder, whole_bytes=DUMP_WHOLE_BYTES, sample=DUMP_SAMPLE):
+    """--dump-outputs: the float32 [B, V, C] feature tensor of the last timed step as .npy files in `folder`.  Up to
+    `whole_bytes` it goes out whole (features.npy); a larger one (cfg2: 256 x 64^3 x 8, 2 GiB) as a fixed, seeded sample of
+    `sample` voxel-channels drawn over the whole batch, in flat [B, V, C] order (features_sample.npy), its first item whole
+    (features_item0.npy, [V, C]) and the float64 sum of every (item, channel) over the grid (features_sums.npy, [B, C])."""
+    import torch
+    os.makedirs(folder, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(folder, name + ".npy"), a)
+    if out.numel() * out.element_size() <= whole_bytes:
+        save("features", out.float().cpu().numpy())
+        return
+    flat = out.reshape(-1)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), size=min(sample, flat.numel()), replace=False))
+    save("features_sample", flat[torch.from_numpy(idx).to(out.device)].float().cpu().numpy())
+    save("features_item0", out[0].float().cpu().numpy())
+    per = max(1, (64 << 20) // max(1, out[0].numel()))          # items per float64 chunk: <= 512 MiB of device memory
+    save("features_sums", torch.cat([out[b:b + per].to(torch.float64).sum(dim=1) for b in range(0, out.shape[0], per)]).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -398,10 +429,17 @@ def main():
                          "worth less than this (<= 1e-5). 0 (default) = the reference's hard 5 A cutoff; reported in `config`")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only: rendezvous (gloo), shard and gather a tiny batch with a stand-in compute; no timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline, the other workloads, the CPU baseline, the sustained "
+                         "steps, the latency probes and (N > 1) the feature gathers.  Off: set-up, warm-up, the timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the features the last step computed (rank 0's items) to DIR/*.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and (args.dry_run or args.workload in ("dist", "dropin")):
+        raise SystemExit("--dump-outputs writes the features of the voxel workloads (cfg1..cfg5), not of --dry-run / dist / dropin")
     if args.gpus > 1 and "RANK" not in os.environ:
         # not under torchrun: become the launcher (one rank per GPU, RCCL), the line comes from rank 0 of the children
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
@@ -494,21 +532,25 @@ def main():
 
     # like the single-grid probe inside run_workload: first, on a quiet GPU, and once more after the batch legs
     dropin0 = None
-    if world == 1 and rank == 0 and not args.no_extra and args.workload == "cfg2":
+    if args.full and world == 1 and rank == 0 and not args.no_extra and args.workload == "cfg2":
         try:
             dropin0 = dropin_probe()
         except Exception as e:                 # noqa: BLE001 -- a secondary number
             dropin0 = f"{type(e).__name__}: {e}"[:300]
     res = run_workload(args.workload, B, args.steps, args.warmup, ctx, dev, rank, world, args, fence,
-                       want_gather=use_dist and not args.no_gather, want_single=rank == 0 and not args.no_single, sustain=True,
-                       defer_gather=True)
+                       want_gather=args.full and use_dist and not args.no_gather, want_single=args.full and rank == 0 and not args.no_single,
+                       sustain=args.full, defer_gather=True, keep=("out",) if args.dump_outputs else ())
     p, nv, V, C, elapsed = res["p"], res["nv"], res["V"], res["C"], res["elapsed"]
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(res["out"], args.dump_outputs)
+        del res["out"]
 
     # secondary legs (every rank takes part; only rank 0 reports).  N = 1: the other BASELINE configs, so that their
     # roofline fractions are timed by whoever runs this file; N > 1: the batched-molecule workload (cfg3) through the
     # same sharded path -- north_star's "batched molecules" -- next to the headline 64^3 workload.
     extra = {}
-    if not args.no_extra and args.workload == "cfg2" and not args.batch:
+    if args.full and not args.no_extra and args.workload == "cfg2" and not args.batch:
         names = ["cfg1", "cfg3", "cfg4", "cfg5"] if world == 1 else ["cfg3"]
         for nm in names:
             ctx.set_lds_tier(args.lds_tier)
@@ -537,7 +579,7 @@ def main():
                 except Exception as e:             # noqa: BLE001
                     extra[nm]["plain_call"] = {"error": f"{type(e).__name__}: {e}"[:200]}
 
-    if not args.no_extra and args.workload == "cfg2" and not args.batch and world == 1 and args.value_tol == 0.0:
+    if args.full and not args.no_extra and args.workload == "cfg2" and not args.batch and world == 1 and args.value_tol == 0.0:
         # the opt-in tolerance-aware reach (mkamd_ctx_set_value_tolerance, eps = 1e-6) on the headline workload: atoms
         # are culled per tile where they are worth less than eps -- a secondary number, the headline keeps the hard cutoff
         try:
@@ -555,7 +597,7 @@ def main():
         finally:
             ctx.set_value_tolerance(0.0)
 
-    if not args.no_extra and args.workload == "cfg2" and not args.batch and world == 1:
+    if args.full and not args.no_extra and args.workload == "cfg2" and not args.batch and world == 1:
         # the package's streaming drivers on cfg4-shaped work: pipelined by promise (device-resident source), and fed from an XTC file
         raw4 = extra.get("cfg4", {}).get("ms_per_step")
         for nm, fn in (("stream_cfg4", bench_stream_cfg4), ("xtc_cfg4", bench_xtc_cfg4)):
@@ -593,24 +635,28 @@ def main():
                            "parallelism": f"dp{world} (items sharded: every rank loads, stages and keeps only its own shard; no collective in the timed region; "
                                           "fences over gloo, feature gathers over RCCL after everything timed)",
                            "device": info["name"], "arch": info["arch"], "compute_units": info["compute_units"]},
-                "roofline": roofline_of(res, args.workload, B, args.tile_k),
-                "tile_kernel_share_of_step": round(k_avg_ms / (elapsed / args.steps * 1e3), 4) if res["k_n"] else None,
-                "sustained": res.get("sustained"),
-                "single_grid_latency_us": round(res["single_us"], 2) if "single_us" in res else None,
-                "single_grid_latency_us_runs": res.get("single_us_runs"),
-                "single_grid_latency_after_batch_load_us": round(res["single_us_after_load"], 2) if "single_us_after_load" in res else None,
-                "gather_ms": round(res["gather_ms"], 3) if "gather_ms" in res else None,
-                "gather_overlapped_extra_ms": round(res["gather_overlapped_extra_ms"], 3) if "gather_overlapped_extra_ms" in res else None,
-                **({"gather_error": res["gather_error"]} if "gather_error" in res else {}),
-                **({"gather_exchange": res["gather_exchange"]} if "gather_exchange" in res else {}),
-                **({"collectives_exercised": res["collectives_exercised"]} if "collectives_exercised" in res else {}),
-                "ranks_alive": alive,
-                **({"degraded": f"a collective between the ranks failed ({_RANKS['broken']}): `value` counts the {alive} rank(s) that finished "
-                                "the timed region, timed on rank 0 alone"} if _RANKS["broken"] else {}),
             }
+            if args.full:
+                line.update({
+                    "roofline": roofline_of(res, args.workload, B, args.tile_k),
+                    "tile_kernel_share_of_step": round(k_avg_ms / (elapsed / args.steps * 1e3), 4) if res["k_n"] else None,
+                    "sustained": res.get("sustained"),
+                    "single_grid_latency_us": round(res["single_us"], 2) if "single_us" in res else None,
+                    "single_grid_latency_us_runs": res.get("single_us_runs"),
+                    "single_grid_latency_after_batch_load_us": round(res["single_us_after_load"], 2) if "single_us_after_load" in res else None,
+                    "gather_ms": round(res["gather_ms"], 3) if "gather_ms" in res else None,
+                    "gather_overlapped_extra_ms": round(res["gather_overlapped_extra_ms"], 3) if "gather_overlapped_extra_ms" in res else None,
+                    **({"gather_error": res["gather_error"]} if "gather_error" in res else {}),
+                    **({"gather_exchange": res["gather_exchange"]} if "gather_exchange" in res else {}),
+                    **({"collectives_exercised": res["collectives_exercised"]} if "collectives_exercised" in res else {}),
+                })
+            line["ranks_alive"] = alive
+            if _RANKS["broken"]:
+                line["degraded"] = (f"a collective between the ranks failed ({_RANKS['broken']}): `value` counts the {alive} rank(s) that finished "
+                                    "the timed region, timed on rank 0 alone")
             if extra:
                 line["other_workloads" if world == 1 else "batched_molecules"] = extra
-            if world == 1 and not args.no_extra and args.workload == "cfg2" and not timed_out:     # (no more GPU work behind a hung leg)
+            if args.full and world == 1 and not args.no_extra and args.workload == "cfg2" and not timed_out:     # (no more GPU work behind a hung leg)
                 try:
                     if isinstance(dropin0, tuple):
                         line["dropin_call_ms"] = round(dropin0[0], 4)
@@ -628,7 +674,7 @@ def main():
                 except Exception as e:             # noqa: BLE001 -- secondary numbers: reported, the headline line still prints
                     line["secondary_error"] = f"{type(e).__name__}: {e}"[:300]
 
-            if world == 1 and not args.no_cpu_baseline and not timed_out:
+            if args.full and world == 1 and not args.no_cpu_baseline and not timed_out:
                 line["cpu_baseline"] = cpu_baseline(args.workload)
             print(json.dumps(line), flush=True)
 

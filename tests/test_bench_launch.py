@@ -125,3 +125,35 @@ def test_bench_dist_workload_shards_frames_over_the_ranks_dry_run():
         assert d["dry_run"] is True and d["n_gpus"] == n and d["ranks_alive"] == n and d["scaling"] == "weak"
         assert d["ok"] is True and d["gather_ok"] is True and d["gather_ms"] is not None and d["value"] > 0
         assert "frames per rank" in d["config"]["workload"] and "no collective" in d["config"]["sharding"]
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): a small feature tensor goes out whole; a larger one as a seeded sample over the whole
+    batch (the same sample every run), the first item whole and the float64 per-item, per-channel sums -- all float32 / float64."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    out = torch.arange(6 * 50 * 8, dtype=torch.float32).reshape(6, 50, 8) / 7
+    bench.dump_outputs(out, str(tmp_path / "whole"))
+    assert sorted(os.listdir(tmp_path / "whole")) == ["features.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "features.npy"), out.numpy())
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d), whole_bytes=1024, sample=100)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["features_item0.npy", "features_sample.npy", "features_sums.npy"]
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    s = np.load(tmp_path / "a" / "features_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (100,) and np.isin(s, out.numpy().ravel()).all() and len(np.unique(s)) == 100
+    assert np.array_equal(np.load(tmp_path / "a" / "features_item0.npy"), out[0].numpy())
+    sums = np.load(tmp_path / "a" / "features_sums.npy")
+    assert sums.dtype == np.float64 and np.allclose(sums, out.double().sum(1).numpy())
+
+
+def test_bench_options_full_and_dump_outputs():
+    """A plain run measures the headline alone; --full adds everything else.  --dump-outputs is refused where it has nothing to write."""
+    r = _run("--help", timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = _run("--workload", "dist", "--dump-outputs", "x", timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr

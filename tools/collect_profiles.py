@@ -1,4 +1,4 @@
-"""Copy the judged summaries of tools/gpu_evidence.sh from gpurun_out/ (scratch) into profiles/<tag>_* (tracked; tag = argv[1], default r5) and stamp every
+"""Copy the judged summaries of tools/gpu_evidence.sh from its scratch folders (the bench lines: bench_logs/) into profiles/<tag>_* (tracked; tag = argv[1], default r5) and stamp every
 PMC summary with the source hash of the library it was taken on (moleculekit_amd._build.built_hash(): bench.py refuses
 counters of another build).  Runs on the GPU box at the end of the evidence session, and again here (idempotent)."""
 import collections
@@ -18,13 +18,13 @@ SRC = _build.built_hash()
 os.makedirs("profiles", exist_ok=True)
 PROF = "--no-cpu-baseline --no-extra --no-single --min-seconds 0 --steps 8 --warmup 2"
 for name in ("cfg2", "cfg2_nopipe", "torchrun1", "dist", "dist_torchrun1"):
-    f = f"gpurun_out/bench_{name}.log"
+    f = f"bench_logs/bench_{name}.log"
     if os.path.exists(f):
         for line in open(f):
             if line.startswith("{"):
                 d = json.loads(line)
                 d["_library_src"] = SRC
-                err = f"gpurun_out/bench_{name}.err"
+                err = f"bench_logs/bench_{name}.err"
                 if os.path.exists(err):                      # the torchrun passes run with NCCL_DEBUG=WARN: what RCCL had to say
                     warn = [l.strip()[:300] for l in open(err, errors="replace") if "NCCL WARN" in l or "NCCL ERROR" in l]
                     d["_nccl_debug_warn_lines"] = warn[:20]

@@ -65,13 +65,15 @@ rpmc sq2 $SQ2
 (timeout 600 python tools/topology_wide_ab.py 2>&1 | grep -v amdgpu > gpurun_out/topology_wide_ab_final.txt)
 grep -a "cutoff shell" gpurun_out/pytest_gpu.log | sort -u; tail -3 gpurun_out/pytest_gpu.log; tail -2 gpurun_out/smoke.log
 python tools/collect_profiles.py $TAG > /dev/null      # the PMC summaries of THIS build first: the bench lines below then carry roofline.traffic
-# the bench lines proper (the default one exactly as the driver runs it), after the counters so that they can quote them
-(timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_cfg2.log 2>&1; echo "rc=$?" >> gpurun_out/bench_cfg2.log)
-(timeout 400 python bench.py --no-cpu-baseline --no-extra --no-pipeline --min-seconds 1 > gpurun_out/bench_cfg2_nopipe.log 2>&1; echo "rc=$?" >> gpurun_out/bench_cfg2_nopipe.log)
-# one rank under torchrun: every collective an N-rank run issues runs on RCCL once (bench.py: collectives_exercised), RCCL's warnings captured
-(NCCL_DEBUG=WARN timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-extra --min-seconds 1 > gpurun_out/bench_torchrun1.log 2> gpurun_out/bench_torchrun1.err; echo "rc=$?" >> gpurun_out/bench_torchrun1.log)
-(NCCL_DEBUG=WARN timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --workload dist --gpus 1 --steps 10 --warmup 3 > gpurun_out/bench_dist_torchrun1.log 2> gpurun_out/bench_dist_torchrun1.err; echo "rc=$?" >> gpurun_out/bench_dist_torchrun1.log)
-(timeout 400 python bench.py --workload dist --steps 20 --warmup 3 > gpurun_out/bench_dist.log 2>&1; echo "rc=$?" >> gpurun_out/bench_dist.log)
+# the bench lines proper (the default one as the driver runs it, with --full: everything it measures), after the counters so that they can quote them;
+# their logs go to bench_logs/, where tools/collect_profiles.py reads them
+mkdir -p bench_logs
+(timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > bench_logs/bench_cfg2.log 2>&1; echo "rc=$?" >> bench_logs/bench_cfg2.log)
+(timeout 400 python bench.py --full --no-cpu-baseline --no-extra --no-pipeline --min-seconds 1 > bench_logs/bench_cfg2_nopipe.log 2>&1; echo "rc=$?" >> bench_logs/bench_cfg2_nopipe.log)
+# one rank under torchrun: every collective an N-rank run issues runs on RCCL once (bench.py --full: collectives_exercised), RCCL's warnings captured
+(NCCL_DEBUG=WARN timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra --min-seconds 1 > bench_logs/bench_torchrun1.log 2> bench_logs/bench_torchrun1.err; echo "rc=$?" >> bench_logs/bench_torchrun1.log)
+(NCCL_DEBUG=WARN timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --workload dist --gpus 1 --steps 10 --warmup 3 > bench_logs/bench_dist_torchrun1.log 2> bench_logs/bench_dist_torchrun1.err; echo "rc=$?" >> bench_logs/bench_dist_torchrun1.log)
+(timeout 400 python bench.py --workload dist --steps 20 --warmup 3 > bench_logs/bench_dist.log 2>&1; echo "rc=$?" >> bench_logs/bench_dist.log)
 python tools/collect_profiles.py $TAG
 # gpurun merges at most 64 MiB back: the per-launch traces are not needed once the stats / counter tables exist
 find gpurun_out -name "*_kernel_trace.csv" -size +1M -delete; du -sh gpurun_out | tail -1

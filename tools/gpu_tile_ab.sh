@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp MKAMD_ALLOW_DIAGNOSTICS=1
 one() {  # label lib args...
   label=$1; lib=$2; shift; shift
-  (MKAMD_LIB=$lib timeout 300 python bench.py --no-cpu-baseline --no-extra --min-seconds 0 --no-single --steps 30 --warmup 5 "$@" 2>&1 | python -c "
+  (MKAMD_LIB=$lib timeout 300 python bench.py --full --no-cpu-baseline --no-extra --min-seconds 0 --no-single --steps 30 --warmup 5 "$@" 2>&1 | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
