@@ -623,7 +623,7 @@ def iterVoxelizeXTC(filename, channels, center, boxsize, voxelsize=1, pbc=True, 
       ``"host"``  by host threads (libmkamd.so's decoder, ``moleculekit_amd.xtc``) into pinned staging, in blocks of 16
                   frames per thread: bound by the host's cores (28 k frames/s of 30 000 atoms on the 16 an MI355X box grants).
       ``"auto"``  the device for a contiguous ascending range of frames whose headers it can take (``xtc.device_decodable``:
-                  no coordinate packed into more than 64 bits, < 2^21 atoms), the host otherwise (a sparse selection would
+                  no coordinate or run of small atoms packed into more than 64 bits, < 2^21 atoms), the host otherwise (a sparse selection would
                   copy the whole span of the file between its first and last frame).
     A frame the device decoder refuses after all, or a corrupt one, raises -- at the latest when the generator ends (like the
     voxelizer's own asynchronous errors)."""

@@ -1730,7 +1730,9 @@ static int xtc_parse_headers(const uint8_t* base, size_t base_off, size_t limit,
         const int64_t f = frames ? frames[j] : j;
         if (f < 0 || f >= (int64_t)idx.offs.size()) return fail(MKAMD_EINVAL, "frame index out of range");
         const size_t r = idx.offs[(size_t)f];
-        if (r < base_off || r + 92 > limit) return fail(MKAMD_EINVAL, "frame outside the bytes handed over");
+        // the record's fixed header is 56 bytes; a compressed one (> 9 atoms) has 36 more before its stream, a raw one (1-9 atoms:
+        // 56 + 12 n bytes in all) may end before byte 92
+        if (r < base_off || r + 56 > limit || (n_atoms > 9 && r + 92 > limit)) return fail(MKAMD_EINVAL, "frame outside the bytes handed over");
         const uint8_t* q = base + (r - base_off);
         if (be_i32(q) != FRAME_MAGIC || (int64_t)be_i32(q + 4) != n_atoms || (int64_t)be_i32(q + 52) != n_atoms) return fail(MKAMD_EINVAL, "corrupt XTC frame");
         step[j] = be_i32(q + 8);

@@ -114,10 +114,15 @@ assert DESC_DTYPE.itemsize == DESC_BYTES
 
 def device_decodable(desc, natoms) -> bool:
     """What the headers tell about ``status 2`` of the device decoder (include/mkamd_xtc.h): no frame of ``desc`` (from
-    ``chunk_desc``) packs a coordinate into more than 64 bits, has >= 2^21 atoms or a stream of >= 512 MB.  (A run of small
-    atoms coded in more than 64 bits is only seen by the device; files with such runs have ranges that fail here.)"""
+    ``chunk_desc``) packs a coordinate into more than 64 bits, has >= 2^21 atoms or a stream of >= 512 MB, or may code a run
+    of small atoms in more than 64 bits.  The last is not a matter of the ranges: the writer picks the header's small-number
+    index from the smallest step between neighbouring atoms (xdrfile.cpp, the ``mindiff`` loop) -- atoms 1 000 nm apart in a
+    file of 1e6 quanta per axis give 65 -- and within a frame the index never exceeds its initial value + 8.  Whether a run
+    actually comes at an index above 64 only the stream tells, so a compressed frame (> 9 atoms) whose header index + 8 exceeds
+    64 is refused: True means the device decodes every frame (status 0); False, that the host decoder should."""
     d = np.ascontiguousarray(desc).view(DESC_DTYPE).reshape(-1)
-    return bool(natoms < (1 << 21) and np.all(d["triple_bits"] <= 64) and np.all(d["nbytes"] < (1 << 29) - 4))
+    runs_fit = natoms <= 9 or bool(np.all(d["smallidx"] + 8 <= 64))
+    return bool(natoms < (1 << 21) and runs_fit and np.all(d["triple_bits"] <= 64) and np.all(d["nbytes"] < (1 << 29) - 4))
 
 
 def chunk_desc(filename, frames, natoms):

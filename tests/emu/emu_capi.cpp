@@ -8,6 +8,7 @@
 #include "../../moleculekit_amd/csrc/xtc_gpu.h"
 #include "../../moleculekit_amd/csrc/host_pack.h"
 
+#include <cstring>
 #include <string>
 #include <algorithm>
 #include <vector>
@@ -326,14 +327,18 @@ int emu_pdist(const float* c, long long n, int D, float* out)
     return run_pdist(be, c, n, D, out, g_err);
 }
 
-// mirrors mkamd_xtc_decode_dev (csrc/capi.hip): the two passes of xtc_gpu.h on host memory; the work buffer is poisoned first
-int emu_xtc_decode(const unsigned char* bytes, const void* desc, long long n_frames, long long n_atoms, float scale, float* xyz, int* status)
+// mirrors mkamd_xtc_decode_dev (csrc/capi.hip): the two passes of xtc_gpu.h on host memory; the work buffer is poisoned first.
+// groups_out (optional: n_frames * (n_atoms + XS_SPEC) records of 2 words) and ngroups_out (n_frames) receive the walk's records
+int emu_xtc_decode(const unsigned char* bytes, const void* desc, long long n_frames, long long n_atoms, float scale, float* xyz, int* status,
+                   unsigned* groups_out, int* ngroups_out)
 {
     if (n_frames <= 0) return 0;
     std::vector<int> ngroups((size_t)n_frames, -1);
     std::vector<XtcGroup> groups((size_t)n_frames * (size_t)(n_atoms + XS_SPEC), XtcGroup{0xCDCDCDCDu, 0xCDCDCDCDu});
     const XtcFrameDesc* D = static_cast<const XtcFrameDesc*>(desc);
     emu::launch(k_xtc_scan, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), bytes, D, n_frames, n_atoms, scale, xyz, groups.data(), ngroups.data(), status);
+    if (groups_out) std::memcpy(groups_out, groups.data(), groups.size() * sizeof(XtcGroup));
+    if (ngroups_out) std::memcpy(ngroups_out, ngroups.data(), ngroups.size() * sizeof(int));
     if (n_atoms >= (1ll << 21)) return 0;
     const long long bpf = (n_atoms + 255) / 256;
     if (bpf == 0) return 0;

@@ -273,15 +273,19 @@ def calculate_occupancy(centers, coords, sigmas, results, inject_lattice_status=
     return st, route.value
 
 
-def xtc_decode(raw, desc, natoms, scale=1.0):
+def xtc_decode(raw, desc, natoms, scale=1.0, groups=False):
     """The device XTC decoder's two kernels (csrc/xtc_gpu.h) on host memory: ``raw`` uint8 (the records + XTC_PAD bytes),
-    ``desc`` uint8 [n, 64] -> (xyz float32 [n, natoms, 3] (poisoned with NaN first), status int32 [n])."""
+    ``desc`` uint8 [n, 64] -> (xyz float32 [n, natoms, 3] (poisoned with NaN first), status int32 [n]); with ``groups`` also the
+    walk's records (uint32 [n, natoms + XS_SPEC, 2]: bit position, ``what``) and their counts (int32 [n], 0 for a refused frame)."""
     raw = np.ascontiguousarray(raw, np.uint8)
     desc = np.ascontiguousarray(desc, np.uint8)
     n = desc.shape[0]
     xyz = np.full((n, natoms, 3), np.nan, np.float32)
     status = np.full(n, -1, np.int32)
-    rc = lib().emu_xtc_decode(_p(raw), _p(desc), ctypes.c_longlong(n), ctypes.c_longlong(natoms), ctypes.c_float(scale), _p(xyz), _p(status))
+    grp = np.zeros((n, natoms + 8, 2), np.uint32) if groups else None       # (XS_SPEC = 8 records of slack per frame)
+    ngrp = np.zeros(n, np.int32) if groups else None
+    rc = lib().emu_xtc_decode(_p(raw), _p(desc), ctypes.c_longlong(n), ctypes.c_longlong(natoms), ctypes.c_float(scale), _p(xyz), _p(status),
+                              _p(grp), _p(ngrp))
     assert rc == 0
-    return xyz, status
+    return (xyz, status, grp, ngrp) if groups else (xyz, status)
 

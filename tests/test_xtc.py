@@ -169,18 +169,9 @@ def test_write_then_read_round_trip_property():
 
 
 def _device_decode_emulated(fn, sel=None, scale=10.0):
-    """The host half of the device decoder (headers, record bytes: libmkamd.so, no GPU involved) + the two kernels of
-    csrc/xtc_gpu.h run by the host SIMT emulation (tests/emu): -> (xyz [n, natoms, 3], status [n])."""
-    import ctypes
-    from tests import emu_build
-    from moleculekit_amd import _lib
-    na, nf = xtc.get_xtc_natoms(fn), xtc.get_xtc_nframes(fn)
-    sel = np.arange(nf, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64)
-    desc, lo, hi, box, t, st = xtc.chunk_desc(fn, sel, na)
-    raw = np.zeros(hi - lo + xtc.XTC_PAD, np.uint8)
-    _lib._check(_lib.load().mkamd_xtc_copy_bytes(xtc._path(fn), lo, hi, raw.ctypes.data_as(ctypes.c_void_p), 1))
-    assert np.array_equal(raw[:hi - lo], np.fromfile(fn, np.uint8, count=hi - lo, offset=lo))
-    return emu_build.xtc_decode(raw, desc, na, scale) + (desc,)
+    """The device decoder emulated on the host (tests/xtc_cases.py), in Angstrom like the voxelizer's feed."""
+    from tests.xtc_cases import device_decode_emulated
+    return device_decode_emulated(fn, sel, scale=scale)
 
 
 def test_device_decoder_kernels_emulated_bit_exact_with_the_host_decoder(tmp_path):
