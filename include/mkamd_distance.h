@@ -126,6 +126,42 @@ int mkamd_cdist_host(mkamd_ctx* ctx, const float* coords1, int64_t n1, const flo
                      int32_t dim, float* results);
 int mkamd_pdist_host(mkamd_ctx* ctx, const float* coords, int64_t n, int32_t dim, float* results);
 
+/* ---- alignment: rigid superposition of frames on a reference structure (moleculekit align.py _pp_align / Molecule.align,
+ * the RMSD of projections/metricrmsd.py) ----
+ * Device layout: frame-major float32 d_xyz [n_frames, n_atoms, 3] (the XTC decoder's and the voxelizer's items), the reference
+ * d_ref [n_ref_frames, n_ref_atoms, 3].  d_sel / d_refsel uint32 [n_sel]: the alignment pairs atom d_sel[k] of a frame with atom
+ * d_refsel[k] of the reference (indices NOT range-checked on the device).  d_frames int64 [n_list] (NULL: frames 0 .. n_list - 1)
+ * lists the frames; entry i of every per-frame output belongs to d_frames[i].  The reference frame is `refframe`, or with
+ * `matchingframes` the listed frame's own index (then n_ref_frames == n_frames).
+ * Transform i is the optimal PROPER rotation in the least-squares sense (Horn's quaternion; no reflection) as affine float64
+ * [12] = row-major R, then t = c_Q - R c_P -- the layout of mkamd_voxelize_lattice_aug_dev's d_affine (mkamd_voxel.h (3b)), so
+ * it can be handed to the voxelizer as is.  Everything is summed in double in a fixed order: the same bits on every run.
+ * An empty selection gives R = I and NaN translations (the reference's means of nothing), not an error.  Asynchronous on the
+ * context's stream. */
+
+/* d_affine [n_list, 12] (out), d_fit_rmsd [n_list] (out, nullable): sqrt(max(0, E_P + E_Q - 2 lambda_max) / n_sel) */
+int mkamd_align_transforms_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, int64_t n_frames, const float* d_ref,
+                               int64_t n_ref_atoms, int64_t n_ref_frames, const uint32_t* d_sel, const uint32_t* d_refsel,
+                               int64_t n_sel, const int64_t* d_frames, int64_t n_list, int64_t refframe, int matchingframes,
+                               double* d_affine, double* d_fit_rmsd);
+/* d_out[f] = float32(R x + t) (evaluated in double, the voxelizer's operation order) for every atom x of each listed frame
+ * f = d_frames[i] with transform d_affine[i]; other frames of d_out are not touched.  d_out may be d_xyz (in place). */
+int mkamd_align_apply_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, const int64_t* d_frames, int64_t n_list,
+                          const double* d_affine, float* d_out);
+/* d_rmsd [n_list] float32 (out): sqrt(sum_k |float32(R p_k + t) - q_k|^2 / n_sel) over the pairs (d_sel, d_refsel), summed in
+ * double and rounded once -- util.molRMSD of the aligned frame, without writing the aligned coordinates anywhere. */
+int mkamd_align_rmsd_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, int64_t n_frames, const float* d_ref,
+                         int64_t n_ref_atoms, int64_t n_ref_frames, const uint32_t* d_sel, const uint32_t* d_refsel, int64_t n_sel,
+                         const int64_t* d_frames, int64_t n_list, int64_t refframe, int matchingframes, const double* d_affine,
+                         float* d_rmsd);
+/* align.py _pp_align(coords, refcoords, sel, refsel, frames, refframe, matchingframes, inplace=True) on host arrays in the
+ * reference's layout: coords float32 [n_atoms, 3, n_frames] (Molecule.coords), refcoords [n_ref_atoms, 3, n_ref_frames].  Only the
+ * span of frames between the smallest and the largest listed one is uploaded (and the reference's frame, or its listed frames);
+ * only the listed frames of coords are written.  Every input is read before anything is written, so refcoords may be coords. */
+int mkamd_align_host(mkamd_ctx* ctx, float* coords, int64_t n_atoms, int64_t n_frames, const float* refcoords, int64_t n_ref_atoms,
+                     int64_t n_ref_frames, const uint32_t* sel, const uint32_t* refsel, int64_t n_sel, const int64_t* frames,
+                     int64_t n_list, int64_t refframe, int matchingframes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,13 @@ SIGNATURES = {
     "mkamd_ctx_last_dist_kernel": (_c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
     "mkamd_cdist_host": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _vp]),
     "mkamd_pdist_host": (_c_int, [_vp, _vp, _c_i64, _c_i32, _vp]),
+    # include/mkamd_distance.h, alignment
+    "mkamd_align_transforms_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_int,
+                                            _vp, _vp]),
+    "mkamd_align_apply_dev": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
+    "mkamd_align_rmsd_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_int, _vp,
+                                      _vp]),
+    "mkamd_align_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_int]),
 }
 
 _lib = None

@@ -389,7 +389,7 @@ def chunk_plan(n_frames, chunk, ramp=0):
 
 
 def _stream_voxelize(N, fr, fill, scale, has_box, channels, center, boxsize, voxelsize, chunk, device, channel_first, ctx,
-                     max_images, fill_dev=None, pipelined=True, use_topology=None, ramp=0):
+                     max_images, fill_dev=None, pipelined=True, use_topology=None, ramp=0, align=None):
     """Core of the streamed voxelizers.  Host sources: ``fill(coords_np [N,3,n], box_np [3,n] | None, idx)`` produces chunk
     ``idx`` (frame indices) straight into pinned staging; device sources: ``fill_dev(xyz [n,N,3], box [n,3] | None, idx)``
     writes the chunk's frame-major device tensors itself.  Everything a chunk needs on the device -- the upload, the
@@ -399,6 +399,10 @@ def _stream_voxelize(N, fr, fill, scale, has_box, channels, center, boxsize, vox
     beside chunk k-1's tile kernel and nothing the consumer enqueues on its own stream between two chunks can sit in
     front of the inputs.  ``pipelined=False``: the same buffers, the compute stream waits for the event itself and the
     calls run in order (the cross-check of tests/test_gpu_api.py; bit-identical).
+
+    ``align`` (``(ref_xyz [n, 3], sel)`` or None): each chunk's frames are superposed on ``ref_xyz`` over the atoms ``sel`` --
+    their transforms are computed on the copy stream, after the chunk's coordinates and before its event, and handed to the
+    voxelizer as ``affine`` (the coordinates themselves are not rewritten: the binning applies the transform).
 
     Periodic boxes are checked per chunk on the host, where they are already at hand (``_chunk_images``: every edge
     > 10 A, images per atom recomputed from THIS chunk's boxes -- an NPT trajectory may shrink after its first frame);
@@ -457,6 +461,11 @@ def _stream_voxelize(N, fr, fill, scale, has_box, channels, center, boxsize, vox
         d_slab_box = [torch.empty(3 * chunk, dtype=torch.float32, device=dev) for _ in range(2)] if host_source and has_box else None
         d_xyz = [torch.empty((chunk * N, 3), dtype=torch.float32, device=dev) for _ in range(2)]
         d_bx = [torch.empty((chunk, 3), dtype=torch.float32, device=dev) for _ in range(2)] if has_box else [None, None]
+        aligner = None
+        if align is not None:
+            from .align import StreamAligner
+            aligner = StreamAligner(align, N, dev)
+        d_aff = [torch.empty((chunk, 12), dtype=torch.float64, device=dev) for _ in range(2)] if aligner is not None else [None, None]
         main.synchronize()                                        # the constants above (and a device-resident source, as far as
                                                                   # this stream produced it) are complete before any promise is made
         free = [torch.cuda.Event(), torch.cuda.Event()]          # staging buffer i may be overwritten (its H2D is done)
@@ -490,6 +499,8 @@ def _stream_voxelize(N, fr, fill, scale, has_box, channels, center, boxsize, vox
                         run_ctx.frames_to_items_dev(copy.cuda_stream, d_slab_box[slot].data_ptr(), 3, n, n, 1.0, d_bx[slot].data_ptr())
                 else:
                     images[slot] = fill_dev(copy, xyz, d_bx[slot][:n] if has_box else None, idx) or max_images
+                if aligner is not None:
+                    aligner.transforms(copy.cuda_stream, xyz, d_aff[slot][:n])
                 ready[slot].record(copy)
             return idx
 
@@ -508,7 +519,8 @@ def _stream_voxelize(N, fr, fill, scale, has_box, channels, center, boxsize, vox
                     main.wait_event(ready[slot])
                 feats = voxelize_lattice_torch(d_xyz[slot][:n * N], d_offs[:n + 1], None if topo is not None else d_sig[:n * N], d_org[:n], nvoxels,
                                                voxelsize, box=d_bx[slot][:n] if has_box else None, max_images=images[slot], ctx=run_ctx,
-                                               channel_first=channel_first, topology=topo)
+                                               channel_first=channel_first, topology=topo,
+                                               affine=d_aff[slot][:n] if aligner is not None else None)
                 consumed[slot].record(torch.cuda.current_stream(dev))
                 run_ctx.poll_errors()                             # non-blocking: errors of the chunks already finished
                 yield idx, feats
@@ -523,7 +535,7 @@ def _stream_voxelize(N, fr, fill, scale, has_box, channels, center, boxsize, vox
 
 
 def iterVoxelizeTrajectory(coords, channels, center, boxsize, voxelsize=1, box=None, frames=None, chunk=512,
-                           device=None, channel_first=False, ctx=None, pipelined=True):
+                           device=None, channel_first=False, ctx=None, pipelined=True, align=None):
     """Stream a trajectory through the GPU chunk by chunk ("trajectory feeding"): yields
     ``(frame_indices, features)`` with ``features`` a float32 CUDA tensor ``[n, V, C]`` (or ``[n, C, nx, ny, nz]`` with
     ``channel_first``) for ``n <= chunk`` frames at a time.
@@ -536,7 +548,14 @@ def iterVoxelizeTrajectory(coords, channels, center, boxsize, voxelsize=1, box=N
     binning pre-pass with chunk k's tile kernel (``_stream_voxelize``), so the consumer (a model, a reduction) sees a
     steady feed whose rate is the slower of PCIe and the voxelizer.  The tensors are yours to keep: each chunk gets
     fresh memory.
+
+    ``align = (ref_xyz [n, 3] Angstrom, sel)``: every frame is first superposed on ``ref_xyz`` over its atoms ``sel`` (the
+    transforms of ``align.kabsch_transforms``, computed per chunk on the device and fused into the binning as the voxelizer's
+    ``affine``); ``center`` is then in the reference's frame.  Not with a ``box``: the minimum image of an axis-aligned box means
+    nothing after a rotation.
     """
+    if align is not None and box is not None:
+        raise ValueError("align cannot be combined with a periodic box (the minimum image is axis-aligned; a rotation breaks it)")
     on_device = hasattr(coords, "is_cuda") and bool(coords.is_cuda)
     if not on_device:
         coords = np.asarray(coords)
@@ -603,11 +622,11 @@ def iterVoxelizeTrajectory(coords, channels, center, boxsize, voxelsize=1, box=N
             return _chunk_images(box[:, idx], nvoxels, voxelsize) if box is not None else 1
 
     yield from _stream_voxelize(N, fr, fill, 1.0, box is not None, channels, center, boxsize, voxelsize, chunk, device,
-                                channel_first, ctx, max_images, fill_dev=fill_dev, pipelined=pipelined)
+                                channel_first, ctx, max_images, fill_dev=fill_dev, pipelined=pipelined, align=align)
 
 
 def iterVoxelizeXTC(filename, channels, center, boxsize, voxelsize=1, pbc=True, frames=None, chunk=1024, device=None,
-                    channel_first=False, ctx=None, nthreads=0, pipelined=True, decode="auto", ramp=0):
+                    channel_first=False, ctx=None, nthreads=0, pipelined=True, decode="auto", ramp=0, align=None):
     """``iterVoxelizeTrajectory`` fed straight from an XTC file.  ``pbc``: use the frames' box (orthorhombic lengths of the
     box vectors) for the minimum image.  Coordinates are converted from the file's nm to Angstrom on the device, like
     ``readers.XTCread`` does on the host.  ``chunk``: frames per step of the pipeline; ``ramp`` > 0: the first step takes
@@ -626,8 +645,13 @@ def iterVoxelizeXTC(filename, channels, center, boxsize, voxelsize=1, pbc=True, 
                   no coordinate or run of small atoms packed into more than 64 bits, < 2^21 atoms), the host otherwise (a sparse selection would
                   copy the whole span of the file between its first and last frame).
     A frame the device decoder refuses after all, or a corrupt one, raises -- at the latest when the generator ends (like the
-    voxelizer's own asynchronous errors)."""
+    voxelizer's own asynchronous errors).
+
+    ``align = (ref_xyz [n, 3] Angstrom, sel)``: as ``iterVoxelizeTrajectory``'s (needs ``pbc=False``)."""
     import ctypes
+
+    if align is not None and pbc:
+        raise ValueError("align needs pbc=False (the minimum image is axis-aligned; a rotation breaks it)")
 
     from . import xtc as _xtc
     if decode not in ("auto", "gpu", "host"):
@@ -654,7 +678,7 @@ def iterVoxelizeXTC(filename, channels, center, boxsize, voxelsize=1, pbc=True, 
         decode = "gpu" if contiguous and _xtc.device_decodable(_xtc.chunk_desc(filename, fr[:1], natoms)[0], natoms) else "host"
     if decode == "gpu" and len(fr):
         yield from _iter_xtc_gpu(filename, path, natoms, fr, box_lengths, nvoxels, bool(pbc), channels, center, boxsize, voxelsize,
-                                 chunk, device, channel_first, ctx, max_images, int(nthreads), pipelined, ramp)
+                                 chunk, device, channel_first, ctx, max_images, int(nthreads), pipelined, ramp, align)
         return
 
     def fill(dst, dst_box, idx):
@@ -669,11 +693,11 @@ def iterVoxelizeXTC(filename, channels, center, boxsize, voxelsize=1, pbc=True, 
             np.copyto(dst_box, box_lengths(bv))
 
     yield from _stream_voxelize(natoms, fr, fill, 10.0, bool(pbc), channels, center, boxsize, voxelsize, chunk, device,
-                                channel_first, ctx, max_images, pipelined=pipelined, ramp=ramp)
+                                channel_first, ctx, max_images, pipelined=pipelined, ramp=ramp, align=align)
 
 
 def _iter_xtc_gpu(filename, path, natoms, fr, box_lengths, nvoxels, has_box, channels, center, boxsize, voxelsize, chunk, device,
-                  channel_first, ctx, max_images, nthreads, pipelined, ramp=0):
+                  channel_first, ctx, max_images, nthreads, pipelined, ramp=0, align=None):
     """``iterVoxelizeXTC(decode="gpu")``: the chunk source of ``_stream_voxelize`` that decodes on the device.  Per chunk, on
     the host: ``mkamd_xtc_chunk_desc`` (headers -> descriptors, box vectors) and ``mkamd_xtc_copy_bytes`` (the records into
     one of two pinned byte buffers); on an UPLOAD stream the records' H2D (beside the previous chunk's decode); on the copy
@@ -769,7 +793,7 @@ def _iter_xtc_gpu(filename, path, natoms, fr, box_lengths, nvoxels, has_box, cha
         return images
 
     gen = _stream_voxelize(natoms, fr, None, 10.0, has_box, channels, center, boxsize, voxelsize, chunk, device, channel_first,
-                           run_ctx, max_images, fill_dev=fill_dev, pipelined=pipelined, ramp=ramp)
+                           run_ctx, max_images, fill_dev=fill_dev, pipelined=pipelined, ramp=ramp, align=align)
     try:
         for item in gen:
             for ss in range(NS):

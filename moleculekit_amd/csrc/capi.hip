@@ -9,6 +9,7 @@
 #include <atomic>
 #include "pipeline.h"
 #include "dist_pipeline.h"
+#include "align_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "cpu_occupancy.h"
@@ -1895,6 +1896,129 @@ try {
         hipLaunchKernelGGL(mkamd::k_xtc_expand, dim3((unsigned)(nf * bpf)), dim3(256), 0, s, bytes, desc, (long long)f0, (long long)n_atoms,
                            scale, d_xyz, groups, ngroups, (int)bpf);
         HIP_TRY(hipGetLastError());
+    }
+    return MKAMD_OK;
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// alignment (include/mkamd_distance.h "alignment"; align_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+static mkamd::AlignArgs align_args(const float* d_xyz, int64_t N, int64_t F, const float* d_ref, int64_t Nr, int64_t Fr,
+                                   const uint32_t* d_sel, const uint32_t* d_refsel, int64_t n, const int64_t* d_frames, int64_t K,
+                                   int64_t refframe, int matching)
+{
+    mkamd::AlignArgs a;
+    a.xyz = d_xyz; a.n_atoms = N; a.n_frames = F;
+    a.ref = d_ref; a.n_ref_atoms = Nr; a.n_ref_frames = Fr;
+    a.sel = d_sel; a.refsel = d_refsel; a.n = n;
+    a.frames = reinterpret_cast<const long long*>(d_frames); a.n_list = K;
+    a.refframe = refframe; a.matching = matching != 0;
+    return a;
+}
+
+extern "C" int mkamd_align_transforms_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const float* d_ref, int64_t Nr,
+                                          int64_t Fr, const uint32_t* d_sel, const uint32_t* d_refsel, int64_t n, const int64_t* d_frames,
+                                          int64_t K, int64_t refframe, int matching, double* d_affine, double* d_fit_rmsd)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (K > 0 && (!d_xyz || !d_ref || !d_affine || (n > 0 && (!d_sel || !d_refsel)))) return fail(MKAMD_EINVAL, "NULL pointer");
+    std::string err;
+    st = mkamd::run_align_transforms(*ctx, align_args(d_xyz, N, F, d_ref, Nr, Fr, d_sel, d_refsel, n, d_frames, K, refframe, matching),
+                                     d_affine, d_fit_rmsd, err);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_align_apply_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, const int64_t* d_frames, int64_t K,
+                                     const double* d_affine, float* d_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N > 0 && K > 0 && (!d_xyz || !d_affine || !d_out)) return fail(MKAMD_EINVAL, "NULL pointer");
+    if ((((uintptr_t)d_xyz) | ((uintptr_t)d_out)) & 3) return fail(MKAMD_EINVAL, "coordinates must be 4-byte aligned");
+    std::string err;
+    st = mkamd::run_align_apply(*ctx, d_xyz, N, reinterpret_cast<const long long*>(d_frames), K, d_affine, d_out, err);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_align_rmsd_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const float* d_ref, int64_t Nr, int64_t Fr,
+                                    const uint32_t* d_sel, const uint32_t* d_refsel, int64_t n, const int64_t* d_frames, int64_t K,
+                                    int64_t refframe, int matching, const double* d_affine, float* d_rmsd)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (K > 0 && (!d_xyz || !d_ref || !d_affine || !d_rmsd || (n > 0 && (!d_sel || !d_refsel)))) return fail(MKAMD_EINVAL, "NULL pointer");
+    std::string err;
+    st = mkamd::run_align_rmsd(*ctx, align_args(d_xyz, N, F, d_ref, Nr, Fr, d_sel, d_refsel, n, d_frames, K, refframe, matching),
+                               d_affine, d_rmsd, err);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_align_host(mkamd_ctx* ctx, float* coords, int64_t N, int64_t F, const float* refcoords, int64_t Nr, int64_t Fr,
+                                const uint32_t* sel, const uint32_t* refsel, int64_t n, const int64_t* frames, int64_t K, int64_t refframe,
+                                int matching)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || Nr < 0 || Fr < 0 || n < 0 || K < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (K == 0 || N == 0) return MKAMD_OK;
+    if (!coords || !refcoords || !frames || (n > 0 && (!sel || !refsel))) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (matching && Fr != F) return fail(MKAMD_EINVAL, "matchingframes needs a reference with as many frames as the trajectory");
+    if (!matching && (refframe < 0 || refframe >= Fr)) return fail(MKAMD_EINVAL, "refframe out of range");
+    for (int64_t k = 0; k < n; ++k)
+        if ((int64_t)sel[k] >= N || (int64_t)refsel[k] >= Nr) return fail(MKAMD_EINVAL, "selection index out of range");
+    int64_t fmin = F, fmax = -1;
+    for (int64_t i = 0; i < K; ++i) {
+        if (frames[i] < 0 || frames[i] >= F) return fail(MKAMD_EINVAL, "frame index out of range");
+        fmin = std::min(fmin, frames[i]);
+        fmax = std::max(fmax, frames[i]);
+    }
+    const int64_t span = fmax - fmin + 1, rows = 3 * N;
+    // the listed frames' span of [3N][F] -> [3N][span] -> frame-major [span][N][3]; the reference likewise (matchingframes) or its
+    // one frame gathered on the host
+    void *dslab, *dxyz, *dref, *dsel, *drefsel, *dframes, *daff;
+    if ((st = ctx->ensure(WS_A_SLAB, (size_t)rows * span * 4, &dslab))) return st;
+    if ((st = ctx->ensure(WS_A_XYZ, (size_t)rows * span * 4, &dxyz))) return st;
+    HIP_TRY(hipMemcpy2DAsync(dslab, (size_t)span * 4, coords + fmin, (size_t)F * 4, (size_t)span * 4, (size_t)rows, hipMemcpyHostToDevice,
+                             ctx->stream));
+    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dslab, rows, span, span, 1.0f, (float*)dxyz))) return st;
+    int64_t ref_frames = 1, rf = 0;
+    if (matching) {
+        if ((st = ctx->ensure(WS_A_REF, (size_t)3 * Nr * span * 4, &dref))) return st;
+        HIP_TRY(hipMemcpy2DAsync(dslab, (size_t)span * 4, refcoords + fmin, (size_t)Fr * 4, (size_t)span * 4, (size_t)(3 * Nr),
+                                 hipMemcpyHostToDevice, ctx->stream));     // (stream order: the transpose above has read the slab)
+        if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dslab, 3 * Nr, span, span, 1.0f, (float*)dref))) return st;
+        ref_frames = span;
+    } else {
+        std::vector<float> r((size_t)3 * Nr);
+        for (int64_t k = 0; k < 3 * Nr; ++k) r[(size_t)k] = refcoords[k * Fr + refframe];
+        if ((st = upload(ctx, WS_A_REF, r.data(), r.size() * 4, &dref))) return st;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                      // (r is a local)
+    }
+    std::vector<int64_t> rel((size_t)K);
+    for (int64_t i = 0; i < K; ++i) rel[(size_t)i] = frames[i] - fmin;
+    if ((st = upload(ctx, WS_A_SEL, sel, (size_t)n * 4, &dsel))) return st;
+    if ((st = upload(ctx, WS_A_REFSEL, refsel, (size_t)n * 4, &drefsel))) return st;
+    if ((st = upload(ctx, WS_A_FRAMES, rel.data(), (size_t)K * 8, &dframes))) return st;
+    if ((st = ctx->ensure(WS_A_AFFINE, (size_t)K * 12 * 8, &daff))) return st;
+    std::string err;
+    st = mkamd::run_align_transforms(*ctx, align_args((const float*)dxyz, N, span, (const float*)dref, Nr, ref_frames, (const uint32_t*)dsel,
+                                                      (const uint32_t*)drefsel, n, (const int64_t*)dframes, K, rf, matching),
+                                     (double*)daff, nullptr, err);
+    if (!st) st = mkamd::run_align_apply(*ctx, (const float*)dxyz, N, (const long long*)dframes, K, (const double*)daff, (float*)dxyz, err);
+    if (st) return err.empty() ? st : fail(st, err);
+    // back to [3N][span], to the host, and only the listed frames into coords
+    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dxyz, span, rows, rows, 1.0f, (float*)dslab))) return st;
+    std::vector<float> out((size_t)rows * span);
+    HIP_TRY(hipMemcpyAsync(out.data(), dslab, out.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int64_t r = 0; r < rows; ++r) {
+        float* dst = coords + r * F;
+        const float* src = out.data() + (size_t)r * span - fmin;
+        for (int64_t i = 0; i < K; ++i) dst[frames[i]] = src[frames[i]];
     }
     return MKAMD_OK;
 } MK_API_CATCH

@@ -38,6 +38,7 @@
 #include "mk_device.h"
 #endif
 
+#include "mk_affine.h"          // MK_AFFINE_APPLY: x' = float32(M x + t), shared with the alignment kernels
 #include "mk_diagnostics.h"     // MK_DIAG / MK_PHASE_* / MK_BIN_*: all zero / empty in a release build (the only -D knobs of this file)
 
 namespace mkamd {
@@ -496,11 +497,7 @@ MK_DEV void bin_atom(const GridDesc& g, long long a, bool act, int b_lo, int b_h
         //  their cycles in s_waitcnt, the kernel is not waiting for memory)
         float xyz[3] = {coords[3 * a + 0], coords[3 * a + 1], coords[3 * a + 2]};
         if (affine != nullptr) {
-            const double* A = affine + 12 * (size_t)b;
-            const double x = (double)xyz[0], y = (double)xyz[1], z = (double)xyz[2];
-            xyz[0] = (float)(A[0] * x + A[1] * y + A[2] * z + A[9]);
-            xyz[1] = (float)(A[3] * x + A[4] * y + A[5] * z + A[10]);
-            xyz[2] = (float)(A[6] * x + A[7] * y + A[8] * z + A[11]);
+            MK_AFFINE_APPLY(affine + 12 * (size_t)b, xyz);
         }
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
@@ -743,11 +740,7 @@ MK_KERNEL(256) void k_bin_direct(GridDesc g, const float* __restrict__ coords, c
     if (want) {
         const int nvox[3] = {g.nx, g.ny, g.nz};
         if (affine != nullptr) {
-            const double* A = affine + 12 * (size_t)b;
-            const double x = (double)xyz[0], y = (double)xyz[1], z = (double)xyz[2];
-            xyz[0] = (float)(A[0] * x + A[1] * y + A[2] * z + A[9]);
-            xyz[1] = (float)(A[3] * x + A[4] * y + A[5] * z + A[10]);
-            xyz[2] = (float)(A[6] * x + A[7] * y + A[8] * z + A[11]);
+            MK_AFFINE_APPLY(affine + 12 * (size_t)b, xyz);
         }
         const double cmid = 0.5 * (double)(g.cs - 1);
         const int nc[3] = {g.ncx, g.ncy, g.ncz};
@@ -909,11 +902,7 @@ MK_KERNEL(256) void k_bin_solo(GridDesc g, const float* __restrict__ coords, con
         }
         const int nvox[3] = {g.nx, g.ny, g.nz};
         if (affine != nullptr) {
-            const double* A = affine + 12 * (size_t)b;
-            const double x = (double)xyz[0], y = (double)xyz[1], z = (double)xyz[2];
-            xyz[0] = (float)(A[0] * x + A[1] * y + A[2] * z + A[9]);
-            xyz[1] = (float)(A[3] * x + A[4] * y + A[5] * z + A[10]);
-            xyz[2] = (float)(A[6] * x + A[7] * y + A[8] * z + A[11]);
+            MK_AFFINE_APPLY(affine + 12 * (size_t)b, xyz);
         }
         const double cmid = 0.5 * (double)(g.cs - 1);
         const int nc[3] = {g.ncx, g.ncy, g.ncz};
@@ -2779,11 +2768,7 @@ MK_DEV void exact_recompute(const GridDesc& g, int b, int ix, int iy, int iz, un
             const long long a = a_lo + (long long)s_near[i];
             float xyz[3] = {coords[3 * a + 0], coords[3 * a + 1], coords[3 * a + 2]};
             if (affine != nullptr) {                                       // rounded to float32 like the binning (bin_atom)
-                const double* A = affine + 12 * (size_t)b;
-                const double x = (double)xyz[0], y = (double)xyz[1], z = (double)xyz[2];
-                xyz[0] = (float)(A[0] * x + A[1] * y + A[2] * z + A[9]);
-                xyz[1] = (float)(A[3] * x + A[4] * y + A[5] * z + A[10]);
-                xyz[2] = (float)(A[6] * x + A[7] * y + A[8] * z + A[11]);
+                MK_AFFINE_APPLY(affine + 12 * (size_t)b, xyz);
             }
             double dx = (double)xyz[0] - cx, dy = (double)xyz[1] - cy, dz = (double)xyz[2] - cz;
             if (g.pbc) {
@@ -2883,11 +2868,7 @@ MK_DEV void exact_fixup_atom(const GridDesc& g, const int b, const long long a, 
     // position in voxel units, as the binning sees it
     float xyz[3] = {coords[3 * a + 0], coords[3 * a + 1], coords[3 * a + 2]};
     if (affine != nullptr) {
-        const double* A = affine + 12 * (size_t)b;
-        const double x = (double)xyz[0], y = (double)xyz[1], z = (double)xyz[2];
-        xyz[0] = (float)(A[0] * x + A[1] * y + A[2] * z + A[9]);
-        xyz[1] = (float)(A[3] * x + A[4] * y + A[5] * z + A[10]);
-        xyz[2] = (float)(A[6] * x + A[7] * y + A[8] * z + A[11]);
+        MK_AFFINE_APPLY(affine + 12 * (size_t)b, xyz);
     }
     double p[3], Lv[3] = {0.0, 0.0, 0.0};
     int k0[3] = {0, 0, 0}, k1[3] = {0, 0, 0};

@@ -39,6 +39,8 @@ enum WsSlot {
     // distance_utils row (dist_pipeline.h)
     WS_D_PA, WS_D_PB, WS_D_WRAP, WS_D_COM1, WS_D_COM2, WS_D_SEL1, WS_D_SEL2, WS_D_CHAINS, WS_D_CHAINS2, WS_D_G1A, WS_D_G1O,
     WS_D_G2A, WS_D_G2O, WS_D_MASS, WS_D_CNT, WS_D_TOT, WS_D_BASE, WS_D_CONTACTS, WS_D_MASK,
+    // alignment (align_pipeline.h) and its host entry point
+    WS_A_REFPART, WS_A_PART, WS_A_RPART, WS_A_FOLD, WS_A_REFFOLD, WS_A_SLAB, WS_A_XYZ, WS_A_REF, WS_A_SEL, WS_A_REFSEL, WS_A_FRAMES, WS_A_AFFINE,
     WS_NSLOTS
 };
 

@@ -1,0 +1,180 @@
+"""GPU tier of the alignment row (moleculekit_amd/align.py): the reference's own alignment and MetricRmsd answers on its trajectory
+(tests/golden/align_cases.npz, tests/golden/make_golden_align.py), a large trajectory against a float64 restatement, and the
+aligned voxel streams against aligned-then-voxelized frames."""
+import os
+
+import numpy as np
+import pytest
+
+from tests.cases import TOL
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "align_cases.npz")
+XTC = os.path.join(HERE, "golden", "xtc", "metricdistance_traj.xtc")
+
+
+def _traj():
+    """the committed trajectory through the project's own reader, in Angstrom like the reference's (x 10 in float32)"""
+    from moleculekit_amd import xtc
+    n = xtc.get_xtc_nframes(XTC)
+    c = xtc.read_xtc_frames(XTC, np.arange(n))[0]
+    return np.ascontiguousarray(c * np.float32(10.0))
+
+
+def kabsch64(P, Q):
+    P = np.asarray(P, np.float64)
+    Q = np.asarray(Q, np.float64)
+    cP, cQ = P.mean(0), Q.mean(0)
+    V, S, Wt = np.linalg.svd((P - cP).T @ (Q - cQ))
+    Z = np.eye(3)
+    Z[2, 2] = np.sign(np.linalg.det(Wt.T) * np.linalg.det(V))
+    R = Wt.T @ Z @ V.T
+    return R, cQ - R @ cP
+
+
+@pytest.mark.parametrize("case", ["selfalign", "refmol", "matching", "selected"])
+def test_molecule_align_cases_match_reference(hip_ctx, case):
+    from moleculekit_amd import align
+    g = np.load(GOLDEN)
+    coords = _traj()
+    lig = np.ascontiguousarray(coords[g["lig_idx"]])
+    assert np.abs(lig - g["lig_coords"]).max() <= 1e-5
+    lig = g["lig_coords"].copy()
+    sel, refsel, frames = g[f"{case}_sel"], g[f"{case}_refsel"], g[f"{case}_frames"]
+    if case == "selfalign":
+        refc = lig
+    elif case == "matching":
+        refc = np.ascontiguousarray(np.roll(lig, 3, axis=2))
+    else:
+        refc = np.ascontiguousarray(lig[sel][:, :, 3:4])
+    before = lig.copy()
+    align._pp_align(lig, refc, sel, refsel, frames, int(g[f"{case}_refframe"]), bool(g[f"{case}_matching"]), inplace=True, ctx=hip_ctx)
+    held = np.abs(lig - g[f"{case}_held"]).max()
+    real = np.abs(lig - g[f"{case}_real"]).max()
+    print(f"{case}: worst gap vs the reference-held array {held:.2e}, vs the real _pp_align {real:.2e}")
+    assert held < 1e-3 and real < 1e-3
+    others = np.setdiff1d(np.arange(lig.shape[2]), frames)
+    assert np.array_equal(lig[:, :, others], before[:, :, others])
+
+
+@pytest.mark.parametrize("name", ["reflected", "coplanar", "oneatom"])
+def test_extra_cases_match_real_pp_align(hip_ctx, name):
+    from moleculekit_amd import align
+    g = np.load(GOLDEN)
+    k = f"extra_{name}_"
+    out = align._pp_align(g[k + "coords"], g[k + "ref"], g[k + "sel"], g[k + "refsel"], g[k + "frames"], 0, False, ctx=hip_ctx)
+    assert np.abs(out - g[k + "out"]).max() < 1e-3
+
+
+def test_rmsd_trajectory_reproduces_metricrmsd(hip_ctx):
+    import torch
+    from moleculekit_amd import align
+    g = np.load(GOLDEN)
+    coords = _traj()
+    dev = torch.device("cuda", hip_ctx.device)
+    xyz = torch.as_tensor(np.ascontiguousarray(coords.transpose(2, 0, 1)), device=dev)
+    ca = g["rmsd_ca_idx"]
+    got = align.rmsd_trajectory(xyz, xyz[0], ca, ca, ctx=hip_ctx).cpu().numpy()
+    torch.cuda.synchronize()
+    print(f"MetricRmsd: worst gap vs known {np.abs(got[-20:] - g['rmsd_known']).max():.2e}, vs the reference's values "
+          f"{np.abs(got - g['rmsd_nopbc']).max():.2e}")
+    assert np.all(np.abs(got[-20:] - g["rmsd_known"]) < 1e-3)
+    assert np.abs(got - g["rmsd_nopbc"]).max() < 1e-4
+    assert np.abs(got - g["rmsd_pbc"]).max() < 1e-4
+    sub = align.rmsd_trajectory(xyz, xyz[0], ca, ca, frames=np.arange(180, 200), ctx=hip_ctx).cpu().numpy()
+    assert np.array_equal(sub, got[180:])
+
+
+def test_large_trajectory_within_one_ulp_and_deterministic(hip_ctx):
+    import torch
+    from moleculekit_amd import align
+    rng = np.random.default_rng(12)
+    N, F, nsel = 30000, 256, 3000
+    ref = (rng.normal(size=(N, 3)) * 20).astype(np.float32)
+    xyz = np.empty((F, N, 3), np.float32)
+    for f in range(F):
+        q = rng.normal(size=4)
+        q /= np.linalg.norm(q)
+        w, x, y, z = q
+        R = np.array([[w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                      [2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)],
+                      [2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z]])
+        xyz[f] = ref @ R.T + rng.uniform(-1000, 1000, 3) + rng.normal(scale=0.5, size=(N, 3))
+    sel = np.sort(rng.choice(N, nsel, replace=False))
+    dev = torch.device("cuda", hip_ctx.device)
+    d_xyz = torch.as_tensor(xyz, device=dev)
+    d_ref = torch.as_tensor(ref, device=dev)
+    aff, fit = align.kabsch_transforms(d_xyz, d_ref, sel, ctx=hip_ctx)
+    out = align.apply_transforms(d_xyz, aff, ctx=hip_ctx)
+    aff2, fit2 = align.kabsch_transforms(d_xyz, d_ref, sel, ctx=hip_ctx)
+    out2 = align.apply_transforms(d_xyz, aff2, ctx=hip_ctx)
+    got, a = out.cpu().numpy(), aff.cpu().numpy()
+    assert torch.equal(aff, aff2) and torch.equal(fit, fit2) and torch.equal(out, out2)
+    worst = 0.0
+    for f in range(0, F, 16):
+        R, t = kabsch64(xyz[f][sel], ref[sel])
+        exp = (xyz[f].astype(np.float64) @ R.T + t).astype(np.float32)
+        ulps = np.abs(got[f].astype(np.float64) - exp) / np.spacing(np.abs(exp)).astype(np.float64)
+        worst = max(worst, float(ulps.max()))
+        assert np.abs(a[f, :9] - R.ravel()).max() < 1e-9
+    print(f"30 000 atoms x 256 frames: worst {worst:.2f} ulp vs the float64 restatement")
+    assert worst <= 1.0
+    # frames outside the list are bitwise untouched (in place)
+    frames = np.array([7, 3, 200])
+    inplace = d_xyz.clone()
+    aff3, _ = align.kabsch_transforms(inplace, d_ref, sel, frames=frames, ctx=hip_ctx)
+    align.apply_transforms(inplace, aff3, frames=frames, out=inplace, ctx=hip_ctx)
+    keep = np.setdiff1d(np.arange(F), frames)
+    assert torch.equal(inplace[keep], d_xyz[keep])
+    assert torch.equal(inplace[frames], out[frames])
+
+
+def test_large_selection_one_frame(hip_ctx):
+    import torch
+    from moleculekit_amd import align
+    rng = np.random.default_rng(13)
+    N = 100000
+    ref = (rng.normal(size=(N, 3)) * 30).astype(np.float32)
+    xyz = (ref[::-1] + 5.0).astype(np.float32)[None]
+    dev = torch.device("cuda", hip_ctx.device)
+    aff, fit = align.kabsch_transforms(torch.as_tensor(xyz, device=dev), torch.as_tensor(ref, device=dev), np.arange(N), ctx=hip_ctx)
+    R, t = kabsch64(xyz[0], ref)
+    assert np.abs(aff.cpu().numpy()[0, :9] - R.ravel()).max() < 1e-9
+
+
+def test_aligned_xtc_stream_equals_aligned_then_voxelized(hip_ctx):
+    import torch
+    from moleculekit_amd import align, batch, xtc
+    from oracle import oracle
+    g = np.load(GOLDEN)
+    ca = g["rmsd_ca_idx"]
+    dev = torch.device("cuda", hip_ctx.device)
+    frames = np.arange(40)
+    xyz, _, _, _ = xtc.read_xtc_frames_dev(XTC, frames, scale=10.0, ctx=hip_ctx)
+    N = int(xyz.shape[1])
+    ref = xyz[0, ca].cpu().numpy()
+    center = ref.astype(np.float64).mean(0)
+    rng = np.random.default_rng(0)
+    sig = rng.uniform(1.0, 2.0, size=(N, 2)).astype(np.float32)
+    box = [16, 16, 16]
+    streamed = torch.cat([f for _, f in batch.iterVoxelizeXTC(XTC, sig, center, box, 1.0, pbc=False, frames=frames, chunk=16,
+                                                               ctx=hip_ctx, align=(ref, ca))])
+    aff, _ = align.kabsch_transforms(xyz, torch.as_tensor(ref, device=dev), ca, np.arange(len(ca)), ctx=hip_ctx)
+    aligned = align.apply_transforms(xyz, aff, ctx=hip_ctx)
+    coords = aligned.permute(1, 2, 0).contiguous()                                  # [N, 3, F] on the device
+    direct = torch.cat([f for _, f in batch.iterVoxelizeTrajectory(coords, sig, center, box, 1.0, chunk=16, ctx=hip_ctx)])
+    torch.cuda.synchronize()
+    assert torch.equal(streamed, direct)
+    plain = torch.cat([f for _, f in batch.iterVoxelizeXTC(XTC, sig, center, box, 1.0, pbc=False, frames=frames[:16], chunk=16, ctx=hip_ctx)])
+    assert not torch.equal(plain, streamed[:16])                                    # (the alignment did something)
+    a = aligned.cpu().numpy()
+    nv = np.ceil(np.array(box, np.float64)).astype(int)
+    centers = oracle.grid_centers(center - np.array(box, np.float64) / 2, nv, 1.0)
+    worst = 0.0
+    for f in (0, 17, 39):
+        exp = oracle.calculate_occupancy(centers, a[f], sig)
+        worst = max(worst, float(np.abs(streamed[f].cpu().numpy() - exp).max()))
+    print(f"aligned stream vs oracle: {worst:.2e}")
+    assert worst <= TOL
