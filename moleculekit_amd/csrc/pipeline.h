@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <string>
 #include <cstdlib>
+#include <type_traits>
 
 namespace mkamd {
 
@@ -225,118 +226,14 @@ enum TileFlavour { TILES_PLAIN = 0, TILES_LEAN = 1, TILES_TEAM = 2, TILES_ITEMS 
 constexpr unsigned REDO_BLOCKS = 4096;       // waves of k_exact_redo (they share the jobs)
 constexpr unsigned SHELL_BLOCKS = 16384;     // waves of k_exact_shells (they share the (item, wide atom) jobs)
 constexpr unsigned REDO_CAP = 32768;         // hits the list holds (1 MB); a call with more walks its shells once more and recomputes in place (k_exact_shells<.., true>)
-// what the call's last launch (k_tail: dense tiles + exact cut-off fix-up) needs besides the tile kernel's arguments
-struct TailArgs {
-    unsigned dense_wgs = 0, fix_waves = 0, fix_jobs = 0;
-    unsigned* other_words = nullptr;
-    int per_item = 0;
-    const unsigned* summary = nullptr;
-    const LatticeProblem* P = nullptr;
-    const void* tcls = nullptr;
-    int team_waves = 0;                     // waves per tile of the team kernel (0 = by the number of tiles; 4, 8, 16: K = 4 only)
-    unsigned* solo_counts = nullptr;        // a call binned by k_bin_solo: its counters (+ control words), zeroed by k_tail
-    unsigned solo_n = 0;
-    const void* sigmas = nullptr;           // != nullptr: the sigma matrix k_tail recomputes from (a topology call: the handle's copy)
-    int sigmas_f64 = 0;
-    unsigned* redo_list = nullptr;          // a topology call with wide atoms: k_tail lists its cut-off hits here, k_exact_redo recomputes them
-    unsigned redo_cap = 0;
-};
+constexpr unsigned CLS_ROWS_PER_BLOCK = 128;         // per-block sigma sets one workgroup of the first merge takes
+constexpr long long PIPELINE_MIN_ATOMS = 200000;     // a call this big may run its pre-pass beside the previous call's tile kernel
 
-template <int K, int T, class BE>
-int launch_tiles_tier(BE& be, int flavour, dim3 tgrid, const TailArgs& ta, const GridDesc& g, void* start, void* rpos, void* rw, void* rcls,
-                      void* ctab, float* out, unsigned* dcount, void* dlist, void* eflag)
-{
-    constexpr int E = ECAP_TIER[T];
-    int st;
-    const bool lean = flavour == TILES_LEAN;
-    if (flavour == TILES_ITEMS) {     // batches of ligand-sized items: a workgroup per item, its entries sorted once
-        // one workgroup per item when there are enough items to fill the chip (4 096 waves), else several per item
-        const long long want_blocks = 1024;
-        long long nchunk = (want_blocks + g.B - 1) / g.B;
-        const long long max_chunk = (g.ntiles + TILE_TEAM - 1) / TILE_TEAM;
-        nchunk = nchunk < 1 ? 1 : (nchunk > max_chunk ? max_chunk : nchunk);
-        int tpb = (int)((g.ntiles + nchunk - 1) / nchunk);
-        tpb = ((tpb + TILE_TEAM - 1) / TILE_TEAM) * TILE_TEAM;
-        const unsigned blocks_per_item = (unsigned)((g.ntiles + tpb - 1) / tpb);
-        st = be.launch(k_voxelize_items<K>, dim3((unsigned)g.B * blocks_per_item, (unsigned)g.G), dim3(WAVE * TILE_TEAM), g, (const unsigned*)start,
-                       (const float4*)rpos, (const float4*)rw, (const unsigned*)rcls, (const unsigned*)ctab, out, tpb);
-    } else if (flavour == TILES_TEAM) {      // a handful of tiles (one grid per call): a team of waves per tile --
-        // four when that fills the chip (a 64^3 grid: 1 024 tiles), more for fewer tiles (a pocket: 54 tiles of K = 4)
-        auto go = [&](auto kern, int team) {
-            return be.launch(kern, tgrid, dim3((unsigned)(WAVE * team)), g, (const unsigned*)start, (const float4*)rpos, (const float4*)rw,
-                             (const unsigned*)rcls, (const unsigned*)ctab, out, dcount, (unsigned*)dlist);
-        };
-        const unsigned long long tw = (unsigned long long)g.B * (unsigned)g.ntiles * (unsigned)g.G;
-        // (the 3PTB pocket, 54 tiles: 30.0 us per call with 4 waves per tile, 27.8 with 8, 28.3 with 16; a cfg2 grid, 1 024 tiles:
-        //  39.9 with 4, 46.6 with 8)
-        const int team = ta.team_waves > 0 ? ta.team_waves : (K == 4 && tw <= 256ull) ? 8 : TILE_TEAM;
-        if constexpr (K == 4) {
-            st = team == 16 ? go(k_voxelize_tiles_team<K, E, 16>, 16) : team == 8 ? go(k_voxelize_tiles_team<K, E, 8>, 8) : go(k_voxelize_tiles_team<K, E, TILE_TEAM>, TILE_TEAM);
-        } else {
-            st = go(k_voxelize_tiles_team<K, E, TILE_TEAM>, TILE_TEAM);
-        }
-    } else if constexpr (T <= 1) {    // the biggest tier is LDS-bound to < 3 waves/SIMD anyway: no lean instance of it
-        st = lean ? be.launch(k_voxelize_tiles_lean<K, E>, tgrid, dim3(WAVE), g, (const unsigned*)start, (const float4*)rpos, (const float4*)rw,
-                              (const unsigned*)rcls, (const unsigned*)ctab, out, dcount, (unsigned*)dlist)
-                  : be.launch(k_voxelize_tiles<K, E>, tgrid, dim3(WAVE), g, (const unsigned*)start, (const float4*)rpos, (const float4*)rw,
-                              (const unsigned*)rcls, (const unsigned*)ctab, out, dcount, (unsigned*)dlist);
-    } else {
-        st = be.launch(k_voxelize_tiles<K, E>, tgrid, dim3(WAVE), g, (const unsigned*)start, (const float4*)rpos, (const float4*)rw,
-                       (const unsigned*)rcls, (const unsigned*)ctab, out, dcount, (unsigned*)dlist);
-    }
-    // the tiles left behind (usually none), the statistics for the next call and the exact cut-off fix-up: one launch
-    if (!st && ta.dense_wgs + ta.fix_waves != 0u) {
-        const LatticeProblem& P = *ta.P;
-        // a topology call with wide atoms: k_tail keeps its dense tiles and bookkeeping, the shells of the wide atoms run in a launch of
-        // their own (k_exact_shells: waves without the dense role's LDS footprint), their hits in a third (k_exact_redo)
-        const bool split = ta.redo_list != nullptr;
-        const unsigned tail_fix_waves = split ? 1u : ta.fix_waves, tail_fix_jobs = split ? 0u : ta.fix_jobs;   // (one wave stays for k_tail's housekeeping)
-        auto tail = [&](auto kern, auto* sig) {
-            return be.launch(kern, dim3(ta.dense_wgs + tail_fix_waves), dim3(WAVE), g, ta.dense_wgs, (const unsigned*)start, (const float4*)rpos,
-                             (const unsigned*)rcls, (const unsigned*)ctab, out, dcount, ta.other_words, (const unsigned*)dlist,
-                             g.force_general ? (unsigned*)nullptr : be.feedback_dev(), (const int*)eflag, ta.per_item, ta.summary, P.coords,
-                             P.atom_offsets, P.total_atoms, sig, P.origins, P.box, P.affine, (const uint2*)ta.tcls, ta.solo_counts, ta.solo_n,
-                             (unsigned*)ctab, g.force_general ? 0u : P.seq, tail_fix_jobs);
-        };
-        const void* sig = ta.sigmas ? ta.sigmas : P.sigmas;
-        const int sig64 = ta.sigmas ? ta.sigmas_f64 : P.sigmas_f64;
-        st = sig64 ? tail(k_tail<K, E, double>, (const double*)sig) : tail(k_tail<K, E, float>, (const float*)sig);
-        if (!st && split) {
-            auto shells = [&](auto kern, auto* sg) {
-                return be.launch(kern, dim3(ta.fix_jobs < SHELL_BLOCKS ? ta.fix_jobs : SHELL_BLOCKS), dim3(WAVE), g, ta.fix_jobs, ta.summary, P.coords, P.atom_offsets,
-                                 P.total_atoms, sg, P.origins, P.box, P.affine, (const uint2*)ta.tcls, out, ta.redo_list, ta.redo_cap);
-            };
-            st = sig64 ? shells(k_exact_shells<double, false>, (const double*)sig) : shells(k_exact_shells<float, false>, (const float*)sig);
-        }
-        if (!st && split) {
-            // the listed hits, a wave per (hit, slice of the item's atoms); blocks that find the list empty leave at once
-            auto redo = [&](auto kern, auto* sg) {
-                return be.launch(kern, dim3(REDO_BLOCKS), dim3(WAVE), g, ta.redo_list, ta.redo_cap, P.coords, P.atom_offsets, sg, P.origins, P.box, P.affine, out);
-            };
-            st = sig64 ? redo(k_exact_redo<double>, (const double*)sig) : redo(k_exact_redo<float>, (const float*)sig);
-        }
-        if (!st && split) {
-            // the list was full (REDO_CAP hits in one call)?  Then every shell once more, recomputed in place; else these blocks leave at once
-            auto again = [&](auto kern, auto* sg) {
-                return be.launch(kern, dim3(ta.fix_jobs < 8192u ? ta.fix_jobs : 8192u), dim3(WAVE), g, ta.fix_jobs, ta.summary, P.coords, P.atom_offsets,
-                                 P.total_atoms, sg, P.origins, P.box, P.affine, (const uint2*)ta.tcls, out, ta.redo_list, ta.redo_cap);
-            };
-            st = sig64 ? again(k_exact_shells<double, true>, (const double*)sig) : again(k_exact_shells<float, true>, (const float*)sig);
-        }
-    }
-    return st;
-}
-
-template <int K, class BE>
-int launch_tiles(BE& be, int tier, int flavour, dim3 tgrid, const TailArgs& ta, const GridDesc& g, void* start, void* rpos, void* rw, void* rcls,
-                 void* ctab, float* out, unsigned* dcount, void* dlist, void* eflag)
-{
-    switch (tier) {
-    case 0: return launch_tiles_tier<K, 0>(be, flavour, tgrid, ta, g, start, rpos, rw, rcls, ctab, out, dcount, dlist, eflag);
-    case 1: return launch_tiles_tier<K, 1>(be, flavour, tgrid, ta, g, start, rpos, rw, rcls, ctab, out, dcount, dlist, eflag);
-    default: return launch_tiles_tier<K, 2>(be, flavour, tgrid, ta, g, start, rpos, rw, rcls, ctab, out, dcount, dlist, eflag);
-    }
-}
+// The one float / double switch on the sigmas: `launch` is a generic lambda that takes the typed sigma pointer and names
+// its kernel instance with sigma_of<decltype(sig)>, so that every argument list is written once.
+template <class Ptr> using sigma_of = std::remove_const_t<std::remove_pointer_t<Ptr>>;
+template <class F>
+inline int with_sigmas(const void* sigmas, int f64, F&& launch) { return f64 ? launch((const double*)sigmas) : launch((const float*)sigmas); }
 
 // What a backend remembers about the cell-counter buffer of one workspace set (run_lattice): which allocation it is and
 // how many of its leading bytes are known to be zero between calls.
@@ -348,6 +245,374 @@ struct CounterState { void* ptr = nullptr; size_t clean = 0; void* wptr = nullpt
                       void* dptr = nullptr; size_t dclean = 0; void* tptr = nullptr; };
 constexpr int DENSE_SET_WORDS = DENSE_WORDS + 2;     // + the done counter of k_tail's dense blocks + its role tickets
 
+// Which kernels a lattice call runs: decided once, from the problem and its grid alone (choose_lattice_path), and finished
+// once the backend has said whether the call is pipelined (settle_lattice_path).  All paths compute the same bits.
+struct LatticePath {
+    // the pre-pass: the kernel chain (count -> classes + scan -> fill; with a topology its TOPO binning kernels), the
+    // one-launch per-item form (k_prepass_items), or the one-launch form of a small call (k_bin_solo)
+    enum PrePass { PRE_CHAIN, PRE_CHAIN_TOPO, PRE_ITEMS, PRE_SOLO } prepass = PRE_CHAIN;
+    bool pipelined_wanted = false;          // what acquire_set() is asked
+    bool team = false;                      // fewer tile waves than the chip has SIMDs: a team of waves per tile
+    bool ligand_items = false;              // ligand-sized items (and the caller has not switched the workgroup-per-item kernel off)
+    bool direct_geom = false;               // the geometry allows a direct record layout (k_bin_direct, k_bin_solo):
+    int direct_cap = 128; unsigned spill = 0; unsigned long long direct_slots = 0;   // its record slots per cell, spill slots PER ITEM, slots in all
+    int team_waves = TILE_TEAM;             // waves per tile of the team kernel
+    // the exact cut-off fix-up: its jobs (256-atom blocks, items, or (item, wide atom) pairs of a topology call), k_tail's waves that
+    // share them, and k_tail's workgroups for the tiles left behind
+    unsigned fix_jobs = 0, fix_waves = 0, dense_wgs = 0;
+    bool split_exact_fixup = false;         // k_tail + k_exact_shells + k_exact_redo instead of k_tail alone
+    unsigned redo_cap = REDO_CAP;           // hits its list holds
+    // settled after acquire_set():
+    bool direct_layout = false;             // the records go to the direct layout (PRE_SOLO, or direct_first)
+    bool direct_first = false;              // k_bin_direct in front of the chain (then the chain is the fall-back)
+    bool small_scan = false;                // the chain's classes + scan in one launch (k_prepass_small) instead of three
+    int flavour = TILES_PLAIN;              // TileFlavour
+
+    bool topo() const { return prepass == PRE_CHAIN_TOPO; }
+    bool solo() const { return prepass == PRE_SOLO; }
+    bool per_item() const { return prepass == PRE_ITEMS; }
+};
+
+inline LatticePath choose_lattice_path(const LatticeProblem& P, const GridDesc& g, bool pipelining_possible)
+{
+    LatticePath L;
+    const bool topo = P.topo != nullptr;
+    const long long B = g.B;
+    // Big batches are software-pipelined across calls: the pre-pass (latency / atomic bound) of this call
+    // runs on an internal stream beside the tile kernel (VALU bound) of the previous call, on the other
+    // workspace set.  Small calls stay in order on the caller's stream (the hand-over costs ~20 us).
+    const bool big = P.total_atoms >= PIPELINE_MIN_ATOMS;
+    // (when the call can be pipelined -- the caller opted in and the batch is big -- items of more than ~1 000 atoms go to
+    //  the kernel chain: its pre-pass then hides behind the previous call's tile kernel, the one-launch one never does;
+    //  cfg1 x 4096 = 1 639 atoms per item: 2.00 -> 1.93 ms per step; 60-atom items lose 4 % that way)
+    const bool chain_pays = pipelining_possible && big && P.total_atoms > 1024LL * B;
+    const unsigned long long tile_waves = (unsigned long long)g.B * (unsigned)g.ntiles * (unsigned)g.G;
+    // fewer tile waves than the chip has SIMDs (one or two 64^3 grids, a pocket): a team of waves per tile --
+    // four when that fills the chip (a 64^3 grid: 1 024 tiles), more for fewer tiles (a pocket: 54 tiles of K = 4)
+    // (the 3PTB pocket, 54 tiles: 30.0 us per call with 4 waves per tile, 27.8 with 8, 28.3 with 16; a cfg2 grid, 1 024 tiles:
+    //  39.9 with 4, 46.6 with 8); 8 and 16 waves: K = 4 only
+    L.team = P.tile_team > 0 || (P.tile_team < 0 && tile_waves <= 1024ull);
+    if (g.K == 4) L.team_waves = (P.tile_team == 8 || P.tile_team == 16) ? P.tile_team : (P.tile_team != 4 && tile_waves <= 256ull) ? 8 : TILE_TEAM;
+    // direct layouts (k_bin_direct, k_bin_solo): open boundaries, one channel group, tiles that see at most 63 cells
+    auto span = [&](int width) {                     // most cells a tile of `width` voxels (aligned to it) sees along one axis
+        int best = 0;
+        for (int x0 = 0; x0 < std::max(g.cs, width); x0 += width)
+            best = std::max(best, ((x0 + width - 1 + g.rint) >> g.cs_log2) - ((x0 - g.rint) >> g.cs_log2) + 1);
+        return best;
+    };
+    static const int env_cap = [] { const char* e = std::getenv("MKAMD_CELL_CAP"); return e ? std::atoi(e) : 0; }();     // A-B knob
+    L.direct_cap = P.cell_cap > 0 ? P.cell_cap : (env_cap > 0 ? env_cap : 128);
+    L.direct_geom = !g.pbc && g.G == 1 && !g.force_general && P.total_atoms > 0 && L.direct_cap <= (1 << SURV_OFF_BITS) &&
+                    span(g.K) * span(8) * span(8) <= WAVE - 1;
+    // many ligand-sized items (cfg3, cfg5): a workgroup per item sorts its entries once for all its tiles
+    L.ligand_items = P.tile_items != 0 && P.total_atoms <= 96LL * B && g.ntiles <= 512;
+    const bool hist_fits = g.ncell + 1 <= ITEM_HIST;         // the cell grid within the LDS counters of k_prepass_items
+    // a SMALL call (the team regime: one molecule per call) takes the one-launch pre-pass k_bin_solo, unless the caller
+    // chose a pre-pass (prepass_mode) or it is a ligand-sized call of the workgroup-per-item tile kernel; direct == 2
+    // forces it for any size (tests)
+    const bool solo = !topo && L.direct_geom && (unsigned long long)P.total_atoms * (unsigned)g.B <= (1ull << 22) &&
+                      (P.direct == 2 || (P.direct != 0 && P.prepass_mode < 0 && L.team && !(L.ligand_items && P.tile_team <= 0 && hist_fits)));
+    // small items (up to a few thousand atoms, cell grid within the LDS counters): the one-launch per-item pre-pass
+    // (short enough that overlapping it with the previous call's tile kernel does not pay: in order, set 0)
+    const bool per_item = !topo && !solo && hist_fits && P.prepass_mode != 0 &&
+                          (P.prepass_mode == 1 || (P.total_atoms <= 4096LL * B && !chain_pays));
+    // a topology call (P.topo): the chain with the TOPO binning kernels
+    L.prepass = topo ? LatticePath::PRE_CHAIN_TOPO : solo ? LatticePath::PRE_SOLO : per_item ? LatticePath::PRE_ITEMS : LatticePath::PRE_CHAIN;
+    L.pipelined_wanted = big && !per_item && !solo;
+    // spill slots PER ITEM (k_bin_solo: every atom of the call, so that it cannot run out)
+    L.spill = solo ? (unsigned)P.total_atoms : P.spill_cap > 0 ? P.spill_cap : (unsigned)std::max<long long>(1024, P.total_atoms / (8LL * B));
+    L.direct_slots = (unsigned long long)((size_t)g.B * (size_t)g.cstride) * (unsigned)L.direct_cap + (unsigned long long)L.spill * (unsigned)g.B;
+    // the exact cut-off fix-up: jobs per 256-atom block, per item, or per (item, WIDE atom of the molecule) -- the handle lists
+    // them -- or none at all.  (Round 5: one job per item; a wave then walked all of a 30 000-atom frame 64 atoms at a time and
+    // took its wide atoms one after the other.)
+    L.fix_jobs = topo ? (unsigned)(B * P.topo->n_wide) : per_item ? (unsigned)g.B : P.total_atoms > 0 ? (unsigned)ceil_div(P.total_atoms, 256) : 0u;
+    L.fix_waves = L.fix_jobs < 8192u ? L.fix_jobs : 8192u;         // (the fix-up waves share the jobs: see k_tail)
+    // (the general path has no dense tiles; its fix-up waves still run, and its statistics stay what they were)
+    L.dense_wgs = g.force_general ? 0u : (unsigned)(tile_waves < 4096ull ? tile_waves : 4096ull);
+    // a trajectory of a molecule with wide sigmas (ions): the exact recomputes of k_tail's hits are spread over many waves (k_exact_redo)
+    L.split_exact_fixup = topo && P.topo->n_wide != 0u && P.seq == 0u && !g.force_general && P.exact_redo_list >= 0;
+    L.redo_cap = P.exact_redo_list > 0 && (unsigned)P.exact_redo_list < REDO_CAP ? (unsigned)P.exact_redo_list : REDO_CAP;   // (a tiny list: tests of the overflow pass)
+    return L;
+}
+
+// The part of the path that depends on what acquire_set() gave the call (and GridDesc::prepass_hurry, which does too).
+inline void settle_lattice_path(LatticePath& L, const LatticeProblem& P, GridDesc& g, bool set_is_pipelined)
+{
+    // Issue priority of the binning / fill waves that run beside the previous call's tile kernel.  Raised (s_setprio 3)
+    // they take issue slots from the tile waves whenever they are ready; left at 0 they live on the slots the tile
+    // kernel leaves idle, which is cheaper (cfg2 +2..4 % at 16..512 grids per step) as long as the chain still
+    // finishes inside the tile kernel.  It does when the tile kernel has enough work per atom: measured on cfg2's atoms
+    // over smaller grids, the chain is late (-8 %) at 2.2 voxels per atom, in time from 2.8 on; the periodic binning
+    // (one wave per SIMD beside the tile kernel, not two) needs the raised priority up to cfg4's 3.7 at least.
+    g.prepass_hurry = !(set_is_pipelined && !g.pbc && (double)g.B * (double)g.V >= 4.0 * (double)P.total_atoms) ? 1 : 0;
+    // k_bin_direct for a big call: whenever asked for (1), and by itself (-1) when the call is NOT pipelined -- in order
+    // the one-pass form is 3 % faster (the class table of the previous call on the workspace serves; the chain behind
+    // it leaves at once), beside the previous call's tile kernel it gains nothing
+    const bool direct_big = L.prepass == LatticePath::PRE_CHAIN && L.direct_geom &&
+                            (P.direct == 1 || (P.direct < 0 && !set_is_pipelined && P.total_atoms >= PIPELINE_MIN_ATOMS));
+    L.direct_layout = (L.solo() || direct_big) && L.direct_slots <= 0xFFFF0000ull;
+    L.direct_first = L.direct_layout && !L.solo();
+    // a small call (one grid): one launch instead of three dependent ones
+    L.small_scan = !L.direct_layout && (size_t)g.B * (size_t)g.cstride <= SMALL_PREPASS_MAX_CELLS &&
+                   (unsigned)ceil_div(P.total_atoms > 0 ? P.total_atoms : 1, 256) <= SMALL_PREPASS_MAX_BLOCKS;
+    // lean: leave registers for the next call's pre-pass
+    L.flavour = L.team ? TILES_TEAM : (set_is_pipelined ? TILES_LEAN : TILES_PLAIN);
+    if (P.tile_items > 0 ? !L.team : (L.ligand_items && P.tile_team <= 0 && L.per_item())) L.flavour = TILES_ITEMS;
+}
+
+// The workspace of one lattice call, typed: what the kernels' parameters are.
+struct LatticeWorkspace {
+    size_t ncells = 0, count_bytes = 0, direct_bytes = 0;
+    unsigned *dense_count = nullptr, *dense_other = nullptr;     // this call's copy of the dense words, and the next call's
+    unsigned *cell_count = nullptr, *cell_start = nullptr, *direct_count = nullptr, *rec_cls = nullptr, *cls_table = nullptr;
+    float4 *rec_pos = nullptr, *rec_w = nullptr, *tmp_pos = nullptr;
+    uint2 *tmp_idx = nullptr, *tmp_cls = nullptr;
+    int* err_flag = nullptr;
+    unsigned *cls_blocks = nullptr, *cls_l1 = nullptr;           // per-block sigma sets and their first merge (not PRE_ITEMS)
+    unsigned *dense_list = nullptr, *redo_list = nullptr;
+    // the counter book-keeping of the set (CounterState): what this call may vouch for once it has been enqueued in full
+    CounterState* cs = nullptr; size_t clean_after = 0; void* table_before = nullptr;
+};
+
+template <class T, class BE>
+int ensure_as(BE& be, int slot, size_t bytes, T*& p, int set)
+{
+    void* v = nullptr;
+    const int st = be.ensure(slot, bytes, &v, set);
+    return p = static_cast<T*>(v), st;
+}
+
+// The buffers of the pre-pass and what is known to be zero in them; fills in the direct layout's fields of `g`.
+template <class BE>
+int acquire_lattice_workspace(BE& be, const LatticeProblem& P, const LatticePath& L, GridDesc& g, int set, LatticeWorkspace& W)
+{
+    int st;
+    const size_t ncells = W.ncells = (size_t)g.B * (size_t)g.cstride;
+    // (when the counters do need a memset its size is a multiple of 256 bytes: an odd tail costs the runtime a second
+    //  fill kernel)
+    W.count_bytes = (ncells * sizeof(unsigned) + 255) & ~(size_t)255;
+    unsigned* dwords_all = nullptr;
+    if ((st = ensure_as(be, WS_DENSE_WORDS, 2 * DENSE_SET_WORDS * sizeof(unsigned), dwords_all, set))) return st;
+    if ((st = ensure_as(be, WS_CELL_COUNT, W.count_bytes, W.cell_count, set))) return st;
+    if ((st = ensure_as(be, WS_CELL_START, (ncells + 1) * sizeof(unsigned), W.cell_start, set))) return st;
+    // direct binning (k_bin_direct: opt-in, big calls, the chain as its fall-back; k_bin_solo: small calls, nothing behind it)
+    size_t mrec = (size_t)g.M;
+    CounterState& cs = *(W.cs = &be.counter_state(set));
+    if (L.direct_layout) {
+        g.cell_cap = L.direct_cap; g.spill_base = (unsigned)(ncells * (size_t)L.direct_cap); g.spill_cap = L.spill;
+        mrec = std::max<size_t>(mrec, (size_t)L.direct_slots);
+        g.cnt_shift = (L.solo() && ncells <= (1u << 16)) ? SOLO_CNT_SHIFT : 0;        // small calls: the counters spread out (see GridDesc)
+        W.direct_bytes = (((size_t)DIRECT_HEAD + (ncells << g.cnt_shift)) * sizeof(unsigned) + 255) & ~(size_t)255;
+        if ((st = ensure_as(be, WS_DIRECT_COUNT, W.direct_bytes, W.direct_count, set))) return st;
+        if (cs.dptr != W.direct_count) { cs.dptr = W.direct_count; cs.dclean = 0; }
+        // the direct counters and the control words of this call: zero -- k_tail leaves them so after a solo call
+        if (cs.dclean < W.direct_bytes && (st = be.fill(W.direct_count, 0, W.direct_bytes))) return st;
+        cs.dclean = 0;                                  // (vouched for again once this call has been enqueued in full)
+        g.direct_words = W.direct_count;
+    }
+    if ((st = ensure_as(be, WS_REC_POS, mrec * sizeof(float4), W.rec_pos, set))) return st;
+    if ((st = ensure_as(be, WS_REC_W, (L.solo() ? mrec : (size_t)g.M) * sizeof(float4) * 2 * g.G, W.rec_w, set))) return st;
+    if ((st = ensure_as(be, WS_REC_CLS, (g.G == 1 ? mrec : (size_t)g.M) * sizeof(unsigned) * g.G, W.rec_cls, set))) return st;
+    if ((st = ensure_as(be, WS_CLS_TABLE, (L.per_item() ? (size_t)g.B : (size_t)1) * CLS_TABLE_WORDS * sizeof(unsigned), W.cls_table, set))) return st;
+    if ((st = ensure_as(be, WS_ERR, sizeof(int), W.err_flag, 0))) return st;
+    if ((st = ensure_as(be, WS_TMP_POS, (size_t)g.M * sizeof(float4), W.tmp_pos, set))) return st;
+    if ((st = ensure_as(be, WS_TMP_IDX, (size_t)g.M * sizeof(uint2), W.tmp_idx, set))) return st;
+    if ((st = ensure_as(be, WS_TMP_CLS, (size_t)(P.total_atoms > 0 ? P.total_atoms : 1) * g.G * sizeof(uint2), W.tmp_cls, set))) return st;
+
+    if (L.solo()) {
+        g.M = (unsigned)mrec;                       // the record arrays' plane stride (rec_w) is the direct layout's slot count
+        // a table buffer nobody has written yet: k_bin_solo starts from an empty table
+        if (cs.tptr != W.cls_table && (st = be.fill(W.cls_table, 0xff, CLS_TABLE_WORDS * sizeof(unsigned)))) return st;
+    }
+    W.table_before = cs.tptr;
+    cs.tptr = nullptr;                              // (a call that fails half-way leaves no table behind)
+    if (cs.ptr != W.cell_count) { cs.ptr = W.cell_count; cs.clean = 0; }
+    W.clean_after = cs.clean;
+    cs.clean = 0;                                   // nothing is vouched for until this call has been enqueued in full
+    if (cs.wptr != dwords_all || !cs.wclean) {      // new buffer, or a call that failed half-way: both copies from scratch
+        if ((st = be.fill(dwords_all, 0, 2 * DENSE_SET_WORDS * sizeof(unsigned)))) return st;
+        cs.wptr = dwords_all;
+    }
+    cs.wclean = false;
+    W.dense_count = dwords_all + cs.parity * DENSE_SET_WORDS;
+    W.dense_other = dwords_all + (cs.parity ^ 1u) * DENSE_SET_WORDS;
+    if (L.per_item()) return ST_OK;
+    // The counters are zero when a call starts and every call leaves them zero (the scan kernels clear what they
+    // read): the memset -- a launch of its own, 6 us of a one-grid call -- is only
+    // needed for bytes no call has vouched for yet (a new or grown buffer, a call that failed half-way).
+    if (W.clean_after < W.count_bytes) {
+        if ((st = be.fill(W.cell_count, 0, W.count_bytes))) return st;
+        W.clean_after = W.count_bytes;
+    }
+    const unsigned nblk = (unsigned)ceil_div(P.total_atoms > 0 ? P.total_atoms : 1, 256);
+    if ((st = ensure_as(be, WS_CLS_BLOCKS, (size_t)nblk * CLS_BLOCK_SET * sizeof(unsigned), W.cls_blocks, set))) return st;
+    return ensure_as(be, WS_CLS_L1, (size_t)ceil_div(nblk, CLS_ROWS_PER_BLOCK) * MERGE_SET * sizeof(unsigned), W.cls_l1, set);
+}
+
+// PRE_ITEMS: one workgroup per item does the whole pre-pass of its item
+template <class BE>
+int prepass_items(BE& be, const LatticeProblem& P, const GridDesc& g, const LatticeWorkspace& W)
+{
+    // few items: big blocks (latency of the one item matters); many items: small blocks (they fill the chip) --
+    // down to ONE wave per item for ligand-sized items (a block's time is a chain of latencies whatever its
+    // size, and four times as many blocks are resident: cfg3's 32 768 items 343 -> ~90 us)
+    const long long avg = P.total_atoms / (long long)g.B;
+    const unsigned threads = (g.B < 512 && avg > 256) ? 1024u : (g.B >= 2048 && avg <= 64) ? 64u : (g.B >= 2048 && avg <= 128) ? 128u : 256u;
+    return with_sigmas(P.sigmas, P.sigmas_f64, [&](auto* sig) {
+        using S = sigma_of<decltype(sig)>;
+        auto go = [&](auto kern) {
+            return be.launch(kern, dim3((unsigned)g.B), dim3(threads), g, P.coords, P.atom_offsets, P.sigmas, P.origins, P.box, P.affine, W.cell_start,
+                             W.tmp_pos, W.tmp_idx, W.tmp_cls, W.rec_pos, W.rec_w, W.rec_cls, W.cls_table, W.dense_count, W.err_flag);
+        };
+        return g.ncell < 512 ? go(k_prepass_items<S, 512>) : g.ncell < 2048 ? go(k_prepass_items<S, 2048>) : go(k_prepass_items<S, ITEM_HIST>);
+    });
+}
+
+// PRE_SOLO: a small call binned, classed and filled by one launch (its counters: zeroed again by k_tail)
+template <class BE>
+int prepass_solo(BE& be, const LatticeProblem& P, const GridDesc& g, const LatticeWorkspace& W)
+{
+    return with_sigmas(P.sigmas, P.sigmas_f64, [&](auto* sig) {
+        return be.launch(k_bin_solo<sigma_of<decltype(sig)>>, dim3((unsigned)ceil_div(P.total_atoms, 256)), dim3(256), g, P.coords, P.atom_offsets,
+                         P.total_atoms, sig, P.origins, P.affine, W.direct_count, W.rec_pos, W.rec_w, W.rec_cls, W.tmp_cls, W.cls_table, W.cls_blocks);
+    });
+}
+
+// PRE_CHAIN, PRE_CHAIN_TOPO: [k_bin_direct ->] k_bin_count -> classes + scan -> k_bin_fill
+template <class BE>
+int prepass_chain(BE& be, const LatticeProblem& P, const LatticePath& L, const GridDesc& g, const LatticeWorkspace& W, int set)
+{
+    int st;
+    const bool topo = L.topo();
+    const dim3 ablk(256), agrid((unsigned)ceil_div(P.total_atoms > 0 ? P.total_atoms : 1, 256));
+    const unsigned nblk = agrid.x, nfblk = (unsigned)ceil_div((long long)g.M, 256);
+    // behind a direct pass the chain is a fall-back that usually leaves at once: a few thousand workgroups that share
+    // the blocks instead of one each (k_bin_count, k_bin_fill)
+    const dim3 cgrid(L.direct_first && nblk > 4096u ? 4096u : nblk);
+    const dim3 fgrid(L.direct_first && nfblk > 4096u ? 4096u : nfblk);
+    const unsigned nl1 = (unsigned)ceil_div(nblk, CLS_ROWS_PER_BLOCK);
+    const unsigned* dfail = g.direct_words ? g.direct_words + DIRECT_FAILED : nullptr;
+    // the one-pass form first; the chain below is enqueued behind it and returns at once unless the pass gave up
+    if (L.direct_first && (st = with_sigmas(P.sigmas, P.sigmas_f64, [&](auto* sig) {
+            return be.launch(k_bin_direct<sigma_of<decltype(sig)>>, agrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, sig, P.origins, P.affine,
+                             W.direct_count, W.rec_pos, W.rec_cls, W.tmp_cls, W.cls_table, W.cls_blocks);
+        }))) return st;
+    if (P.total_atoms > 0) {
+        auto bin = [&](auto kern, auto* sig) {
+            return be.launch(kern, cgrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, sig, P.origins, P.box, P.affine, W.cell_count, W.tmp_pos,
+                             W.tmp_idx, W.tmp_cls, W.cls_blocks, W.err_flag, nblk);
+        };
+        if (topo) {
+            // the ids stand where the sigmas would (bin_atom<.., TOPO>): the one launch whose argument is not of the buffer's type
+            auto* ids = (const float*)P.topo->ids;
+            st = g.pbc ? bin(k_bin_count<float, 1, false, true>, ids) : bin(k_bin_count<float, 0, false, true>, ids);
+        } else {
+            st = with_sigmas(P.sigmas, P.sigmas_f64, [&](auto* sig) {
+                using S = sigma_of<decltype(sig)>;             // (open boundaries: the direct layouts have no periodic form)
+                return L.direct_first ? bin(k_bin_count<S, 0, true>, sig) : g.pbc ? bin(k_bin_count<S, 1>, sig) : bin(k_bin_count<S, 0>, sig);
+            });
+        }
+        if (st) return st;
+    }
+    // sigma classes (per-block sets -> class table) and the scan of the cell counts, fused two launches deep
+    const bool do_classes = P.total_atoms > 0 && !g.force_general && !topo;
+    if (!do_classes && !topo && (st = be.fill(W.cls_table, 0xff, CLS_TABLE_WORDS * sizeof(unsigned)))) return st;   // nothing to register
+    if (L.small_scan) {
+        if ((st = be.launch(k_prepass_small, dim3(1), dim3(SMALL_PREPASS_THREADS), W.cls_blocks, do_classes ? nblk : 0u, W.cls_table, W.cell_count,
+                            (unsigned)W.ncells, W.cell_start))) return st;
+    } else {
+        const size_t nchunks = (W.ncells + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK;
+        unsigned* chunks = nullptr;
+        if ((st = ensure_as(be, WS_SCAN_CHUNKS, nchunks * sizeof(unsigned), chunks, set))) return st;
+        const unsigned nl1_eff = do_classes ? nl1 : 0u;
+        if ((st = be.launch(k_prepass_reduce1, dim3(nl1_eff + (unsigned)nchunks), dim3(256), W.cls_blocks, nblk, (unsigned)CLS_ROWS_PER_BLOCK, nl1_eff, W.cls_l1,
+                            W.cell_count, W.ncells, chunks, dfail))) return st;
+        if ((st = be.launch(k_prepass_reduce2, dim3(do_classes ? 2u : 1u), dim3(256), W.cls_l1, nl1_eff, W.cls_table, chunks, (unsigned)nchunks, dfail))) return st;
+        if ((st = be.launch(k_scan_finish, dim3((unsigned)nchunks), dim3(SCAN_THREADS), W.cell_count, W.ncells, chunks, W.cell_start, dfail))) return st;
+    }
+    if (P.total_atoms <= 0) return ST_OK;
+    // (FOUR temp slots per thread with their loads in flight together -- for calls that run alone on the chip, where the
+    //  48-register budget does not apply -- were measured: 261 us against 212, the pass is bound by its scattered
+    //  stores, not by the round trips in front of them)
+    auto fill = [&](auto kern, auto* sig) {
+        return be.launch(kern, fgrid, ablk, g, sig, W.cell_start, W.tmp_pos, W.tmp_idx, W.tmp_cls, W.rec_pos, W.rec_w, W.rec_cls, W.cls_table, nfblk);
+    };
+    if (topo) return fill(k_bin_fill<float, false, true>, (const float*)nullptr);
+    return with_sigmas(P.sigmas, P.sigmas_f64, [&](auto* sig) {
+        using S = sigma_of<decltype(sig)>;
+        return L.direct_first ? fill(k_bin_fill<S, true>, sig) : fill(k_bin_fill<S>, sig);
+    });
+}
+
+// The tile kernel of the call's flavour and LDS tier, then the tiles left behind (usually none), the statistics for the
+// next call and the exact cut-off fix-up.
+template <int K, int T, class BE>
+int launch_tiles_tier(BE& be, const LatticeProblem& P, const LatticePath& L, const GridDesc& g, const LatticeWorkspace& W)
+{
+    constexpr int E = ECAP_TIER[T];
+    int st;
+    const unsigned total_tiles = (unsigned)g.B * (unsigned)g.ntiles;
+    auto tiles = [&](auto kern, unsigned waves) {
+        return be.launch(kern, dim3(((total_tiles + 7u) / 8u) * 8u, (unsigned)g.G), dim3(WAVE * waves), g, W.cell_start, W.rec_pos, W.rec_w, W.rec_cls,
+                         W.cls_table, P.out, W.dense_count, W.dense_list);
+    };
+    if (L.flavour == TILES_ITEMS) {     // batches of ligand-sized items: a workgroup per item, its entries sorted once
+        // one workgroup per item when there are enough items to fill the chip (4 096 waves), else several per item
+        long long nchunk = (1024 + g.B - 1) / g.B;
+        const long long max_chunk = (g.ntiles + TILE_TEAM - 1) / TILE_TEAM;
+        nchunk = nchunk < 1 ? 1 : (nchunk > max_chunk ? max_chunk : nchunk);
+        int tpb = (int)((g.ntiles + nchunk - 1) / nchunk);
+        tpb = ((tpb + TILE_TEAM - 1) / TILE_TEAM) * TILE_TEAM;
+        const unsigned blocks_per_item = (unsigned)((g.ntiles + tpb - 1) / tpb);
+        st = be.launch(k_voxelize_items<K>, dim3((unsigned)g.B * blocks_per_item, (unsigned)g.G), dim3(WAVE * TILE_TEAM), g, W.cell_start, W.rec_pos, W.rec_w,
+                       W.rec_cls, W.cls_table, P.out, tpb);
+    } else if (L.flavour == TILES_TEAM) {      // a handful of tiles (one grid per call): a team of waves per tile
+        if constexpr (K == 4) {
+            st = L.team_waves == 16 ? tiles(k_voxelize_tiles_team<K, E, 16>, 16u) : L.team_waves == 8 ? tiles(k_voxelize_tiles_team<K, E, 8>, 8u)
+                                                                                                  : tiles(k_voxelize_tiles_team<K, E, TILE_TEAM>, (unsigned)TILE_TEAM);
+        } else st = tiles(k_voxelize_tiles_team<K, E, TILE_TEAM>, (unsigned)TILE_TEAM);
+    } else if constexpr (T <= 1) {    // the biggest tier is LDS-bound to < 3 waves/SIMD anyway: no lean instance of it
+        st = L.flavour == TILES_LEAN ? tiles(k_voxelize_tiles_lean<K, E>, 1u) : tiles(k_voxelize_tiles<K, E>, 1u);
+    } else {
+        st = tiles(k_voxelize_tiles<K, E>, 1u);
+    }
+    if (st || L.dense_wgs + L.fix_waves == 0u) return st;
+    // a topology call with wide atoms: k_tail keeps its dense tiles and bookkeeping, the shells of the wide atoms run in a launch of
+    // their own (k_exact_shells: waves without the dense role's LDS footprint), their hits in a third (k_exact_redo)
+    const bool split = L.split_exact_fixup;
+    const unsigned tail_fix_waves = split ? 1u : L.fix_waves, tail_fix_jobs = split ? 0u : L.fix_jobs;   // (one wave stays for k_tail's housekeeping)
+    const bool topo = L.topo();
+    // what a fix-up wave of k_tail looks at first (see exact_fixup_block)
+    const unsigned* summary = topo ? P.topo->wide_list : g.force_general ? nullptr : L.per_item() ? W.cls_table : W.cls_blocks;
+    const uint2* cw = topo ? P.topo->cw : W.tmp_cls;
+    // (a topology call recomputes from the handle's copy of the sigma matrix)
+    return with_sigmas(topo ? P.topo->sigmas : P.sigmas, topo ? P.topo->sigmas_f64 : P.sigmas_f64, [&](auto* sig) {
+        using S = sigma_of<decltype(sig)>;
+        int s = be.launch(k_tail<K, E, S>, dim3(L.dense_wgs + tail_fix_waves), dim3(WAVE), g, L.dense_wgs, W.cell_start, W.rec_pos, W.rec_cls, W.cls_table, P.out,
+                          W.dense_count, W.dense_other, W.dense_list, g.force_general ? (unsigned*)nullptr : be.feedback_dev(), W.err_flag,
+                          topo ? 2 : L.per_item() ? 1 : 0, summary, P.coords, P.atom_offsets, P.total_atoms, sig, P.origins, P.box, P.affine, cw,
+                          L.solo() ? W.direct_count : nullptr, L.solo() ? (unsigned)(DIRECT_HEAD + (W.ncells << g.cnt_shift)) : 0u, W.cls_table,
+                          g.force_general ? 0u : P.seq, tail_fix_jobs);
+        if (s || !split) return s;
+        auto shells = [&](auto kern, unsigned max_blocks) {
+            return be.launch(kern, dim3(L.fix_jobs < max_blocks ? L.fix_jobs : max_blocks), dim3(WAVE), g, L.fix_jobs, summary, P.coords, P.atom_offsets,
+                             P.total_atoms, sig, P.origins, P.box, P.affine, cw, P.out, W.redo_list, L.redo_cap);
+        };
+        if ((s = shells(k_exact_shells<S, false>, SHELL_BLOCKS))) return s;
+        // the listed hits, a wave per (hit, slice of the item's atoms); blocks that find the list empty leave at once
+        if ((s = be.launch(k_exact_redo<S>, dim3(REDO_BLOCKS), dim3(WAVE), g, W.redo_list, L.redo_cap, P.coords, P.atom_offsets, sig, P.origins, P.box,
+                           P.affine, P.out))) return s;
+        // the list was full (REDO_CAP hits in one call)?  Then every shell once more, recomputed in place; else these blocks leave at once
+        return shells(k_exact_shells<S, true>, 8192u);
+    });
+}
+
+template <int K, class BE>
+int launch_tiles(BE& be, int tier, const LatticeProblem& P, const LatticePath& L, const GridDesc& g, const LatticeWorkspace& W)
+{
+    return tier == 0 ? launch_tiles_tier<K, 0>(be, P, L, g, W) : tier == 1 ? launch_tiles_tier<K, 1>(be, P, L, g, W) : launch_tiles_tier<K, 2>(be, P, L, g, W);
+}
+
 // The lattice hot path: bin -> scan -> fill -> tile kernel.  All pointers in P are device pointers.
 template <class BE>
 int run_lattice(BE& be, const LatticeProblem& P, std::string& err)
@@ -356,289 +621,58 @@ int run_lattice(BE& be, const LatticeProblem& P, std::string& err)
     int st = plan_lattice(P, g, err);
     if (st) return st;
     if (P.B == 0 || g.V == 0) return ST_OK;
-
-    // Big batches are software-pipelined across calls: the pre-pass (latency / atomic bound) of this call
-    // runs on an internal stream beside the tile kernel (VALU bound) of the previous call, on the other
-    // workspace set.  Small calls stay in order on the caller's stream (the hand-over costs ~20 us).
-    // small items (up to a few thousand atoms, cell grid within the LDS counters): the one-launch per-item pre-pass
-    // (short enough that overlapping it with the previous call's tile kernel does not pay: in order, set 0)
-    // (when the call can be pipelined -- the caller opted in and the batch is big -- items of more than ~1 000 atoms go to
-    //  the kernel chain: its pre-pass then hides behind the previous call's tile kernel, the one-launch one never does;
-    //  cfg1 x 4096 = 1 639 atoms per item: 2.00 -> 1.93 ms per step; 60-atom items lose 4 % that way)
-    // a topology call (P.topo): the chain with the TOPO binning kernels; what they do not cover -- the general path, the
-    // tolerance-aware reach (it needs every atom's smallest w at fill time) -- is refused, not approximated
-    const bool topo = P.topo != nullptr;
-    if (topo) {
-        if (P.topo->overflow || g.force_general || g.reach_tau > 0.f) {
+    // a topology call: what its binning kernels do not cover -- the general path, the tolerance-aware reach (it needs every
+    // atom's smallest w at fill time) -- is refused, not approximated
+    if (const TopologyDev* t = P.topo) {
+        if (t->overflow || g.force_general || g.reach_tau > 0.f) {
             err = "a topology call takes the class-sorted path only: not with more than 15 distinct sigmas, force_general or a value tolerance (use the plain entry point)";
             return ST_EINVAL;
         }
-        if (P.topo->C != P.C || P.topo->voxelsize != P.voxelsize || P.topo->n <= 0 || P.total_atoms != (long long)P.B * P.topo->n) {
+        if (t->C != P.C || t->voxelsize != P.voxelsize || t->n <= 0 || P.total_atoms != (long long)P.B * t->n) {
             err = "the topology was built for another channel count / voxel size, or the call is not n_items x its atom count long";
             return ST_EINVAL;
         }
+        if ((unsigned long long)g.B * t->n_wide > 0xffffffffull) { err = "too many (item, wide atom) fix-up jobs (>= 2^32): split the batch"; return ST_EINVAL; }
+        g.topo_n = t->n; g.topo_wide = t->n_wide;
     }
-    g.topo_n = topo ? P.topo->n : 0;
-    g.topo_wide = topo ? P.topo->n_wide : 0u;
-    const bool chain_pays = be.pipelining_possible() && P.total_atoms >= 200000 && P.total_atoms > 1024LL * (long long)g.B;
-    const unsigned total_tiles = (unsigned)g.B * (unsigned)g.ntiles;
-    // fewer tile waves than the chip has SIMDs (one or two 64^3 grids, a pocket): a team of waves per tile
-    const bool team = P.tile_team > 0 || (P.tile_team < 0 && (unsigned long long)total_tiles * (unsigned)g.G <= 1024ull);
-    // direct layouts (k_bin_direct, k_bin_solo): open boundaries, one channel group, tiles that see at most 63 cells
-    auto span = [&](int width) {                     // most cells a tile of `width` voxels (aligned to it) sees along one axis
-        int best = 0;
-        for (int x0 = 0; x0 < (g.cs > width ? g.cs : width); x0 += width) {
-            const int n = ((x0 + width - 1 + g.rint) >> g.cs_log2) - ((x0 - g.rint) >> g.cs_log2) + 1;
-            best = n > best ? n : best;
-        }
-        return best;
-    };
-    static const int env_cap = [] { const char* e = std::getenv("MKAMD_CELL_CAP"); return e ? std::atoi(e) : 0; }();     // A-B knob
-    const int direct_cap = P.cell_cap > 0 ? P.cell_cap : (env_cap > 0 ? env_cap : 128);
-    const bool direct_geom = !g.pbc && g.G == 1 && !g.force_general && P.total_atoms > 0 && direct_cap <= (1 << SURV_OFF_BITS) &&
-                             span(g.K) * span(8) * span(8) <= WAVE - 1;
-    // a SMALL call (the team regime: one molecule per call) takes the one-launch pre-pass k_bin_solo, unless the caller
-    // chose a pre-pass (prepass_mode) or it is a ligand-sized call of the workgroup-per-item tile kernel; direct == 2
-    // forces it for any size (tests)
-    const bool items_sized = P.tile_items != 0 && P.total_atoms <= 96LL * (long long)g.B && g.ntiles <= 512;
-    const bool solo = !topo && direct_geom && (unsigned long long)P.total_atoms * (unsigned)g.B <= (1ull << 22) &&
-                      (P.direct == 2 || (P.direct != 0 && P.prepass_mode < 0 && team && !(items_sized && P.tile_team <= 0 && g.ncell + 1 <= ITEM_HIST)));
-    const bool per_item = !topo && !solo && (g.ncell + 1 <= ITEM_HIST) && P.prepass_mode != 0 &&
-                          (P.prepass_mode == 1 || (P.total_atoms <= 4096LL * (long long)g.B && !chain_pays));
-    g.cls_per_item = per_item ? 1 : 0;
-    const int set = be.acquire_set(P.total_atoms >= 200000 && !per_item && !solo);
-    // Issue priority of the binning / fill waves that run beside the previous call's tile kernel.  Raised (s_setprio 3)
-    // they take issue slots from the tile waves whenever they are ready; left at 0 they live on the slots the tile
-    // kernel leaves idle, which is cheaper (cfg2 +2..4 % at 16..512 grids per step) as long as the chain still
-    // finishes inside the tile kernel.  It does when the tile kernel has enough work per atom: measured on cfg2's atoms
-    // over smaller grids, the chain is late (-8 %) at 2.2 voxels per atom, in time from 2.8 on; the periodic binning
-    // (one wave per SIMD beside the tile kernel, not two) needs the raised priority up to cfg4's 3.7 at least.
-    g.prepass_hurry = !(be.set_is_pipelined(set) && !g.pbc && (double)g.B * (double)g.V >= 4.0 * (double)P.total_atoms) ? 1 : 0;
-    const size_t ncells = (size_t)g.B * (size_t)g.cstride;
-    void *count = nullptr, *start = nullptr, *rpos = nullptr, *rw = nullptr, *rcls = nullptr, *ctab = nullptr, *eflag = nullptr;
-    void *tpos = nullptr, *tidx = nullptr, *tcls = nullptr;
-    // (when the counters do need a memset its size is a multiple of 256 bytes: an odd tail costs the runtime a second
-    //  fill kernel)
-    const size_t count_bytes = (ncells * sizeof(unsigned) + 255) & ~(size_t)255;
-    void* dwords_all = nullptr;
-    if ((st = be.ensure(WS_DENSE_WORDS, 2 * DENSE_SET_WORDS * sizeof(unsigned), &dwords_all, set))) return st;
-    if ((st = be.ensure(WS_CELL_COUNT, count_bytes, &count, set))) return st;
-    if ((st = be.ensure(WS_CELL_START, (ncells + 1) * sizeof(unsigned), &start, set))) return st;
-    // direct binning (k_bin_direct: opt-in, big calls, the chain as its fall-back; k_bin_solo: small calls, nothing behind it)
-    void* dcnt = nullptr;
-    size_t mrec = (size_t)g.M, dbytes = 0;
-    CounterState& cs = be.counter_state(set);
-    {
-        // spill slots PER ITEM (k_bin_solo: every atom of the call, so that it cannot run out)
-        const unsigned spill = solo ? (unsigned)P.total_atoms
-                                    : P.spill_cap > 0 ? P.spill_cap : (unsigned)std::max<long long>(1024, P.total_atoms / (8LL * g.B));
-        const unsigned long long slots = (unsigned long long)ncells * (unsigned)direct_cap + (unsigned long long)spill * (unsigned)g.B;
-        // k_bin_direct for a big call: whenever asked for (1), and by itself (-1) when the call is NOT pipelined -- in order
-        // the one-pass form is 3 % faster (the class table of the previous call on the workspace serves; the chain behind
-        // it leaves at once), beside the previous call's tile kernel it gains nothing
-        const bool direct_big = !topo && !per_item && direct_geom && (P.direct == 1 || (P.direct < 0 && !be.set_is_pipelined(set) && P.total_atoms >= 200000));
-        const bool direct = (solo || direct_big) && slots <= 0xFFFF0000ull;
-        if (solo && !direct) { err = "internal: the one-launch pre-pass does not fit its record slots"; return ST_EINVAL; }
-        if (direct) {
-            g.cell_cap = direct_cap; g.spill_base = (unsigned)(ncells * (size_t)direct_cap); g.spill_cap = spill;
-            mrec = std::max<size_t>(mrec, (size_t)slots);
-            g.cnt_shift = (solo && ncells <= (1u << 16)) ? SOLO_CNT_SHIFT : 0;        // small calls: the counters spread out (see GridDesc)
-            dbytes = (((size_t)DIRECT_HEAD + (ncells << g.cnt_shift)) * sizeof(unsigned) + 255) & ~(size_t)255;
-            if ((st = be.ensure(WS_DIRECT_COUNT, dbytes, &dcnt, set))) return st;
-            if (cs.dptr != dcnt) { cs.dptr = dcnt; cs.dclean = 0; }
-            // the direct counters and the control words of this call: zero -- k_tail leaves them so after a solo call
-            if (cs.dclean < dbytes && (st = be.fill(dcnt, 0, dbytes))) return st;
-            cs.dclean = 0;                                  // (vouched for again once this call has been enqueued in full)
-            g.direct_words = (const unsigned*)dcnt;
-        }
-    }
-    if ((st = be.ensure(WS_REC_POS, mrec * sizeof(float4), &rpos, set))) return st;
-    if ((st = be.ensure(WS_REC_W, (solo ? mrec : (size_t)g.M) * sizeof(float4) * 2 * g.G, &rw, set))) return st;
-    if ((st = be.ensure(WS_REC_CLS, (g.G == 1 ? mrec : (size_t)g.M) * sizeof(unsigned) * g.G, &rcls, set))) return st;
-    if ((st = be.ensure(WS_CLS_TABLE, (per_item ? (size_t)g.B : (size_t)1) * CLS_TABLE_WORDS * sizeof(unsigned), &ctab, set))) return st;
-    if ((st = be.ensure(WS_ERR, sizeof(int), &eflag, 0))) return st;
-    if ((st = be.ensure(WS_TMP_POS, (size_t)g.M * sizeof(float4), &tpos, set))) return st;
-    if ((st = be.ensure(WS_TMP_IDX, (size_t)g.M * sizeof(uint2), &tidx, set))) return st;
-    if ((st = be.ensure(WS_TMP_CLS, (size_t)(P.total_atoms > 0 ? P.total_atoms : 1) * g.G * sizeof(uint2), &tcls, set))) return st;
+    LatticePath L = choose_lattice_path(P, g, be.pipelining_possible());
+    g.cls_per_item = L.per_item() ? 1 : 0;
+    const int set = be.acquire_set(L.pipelined_wanted);
+    settle_lattice_path(L, P, g, be.set_is_pipelined(set));
+    if (L.solo() && !L.direct_layout) { err = "internal: the one-launch pre-pass does not fit its record slots"; return ST_EINVAL; }
 
-    if (solo) {
-        g.M = (unsigned)mrec;                       // the record arrays' plane stride (rec_w) is the direct layout's slot count
-        if (cs.tptr != ctab) {                      // a table buffer nobody has written yet: k_bin_solo starts from an empty table
-            if ((st = be.fill(ctab, 0xff, CLS_TABLE_WORDS * sizeof(unsigned)))) return st;
-        }
-    }
-    void* const table_before = cs.tptr;
-    cs.tptr = nullptr;                              // (a call that fails half-way leaves no table behind)
-    if (cs.ptr != count) { cs.ptr = count; cs.clean = 0; }
-    size_t clean_after = cs.clean;
-    cs.clean = 0;                                   // nothing is vouched for until this call has been enqueued in full
-    if (cs.wptr != dwords_all || !cs.wclean) {      // new buffer, or a call that failed half-way: both copies from scratch
-        if ((st = be.fill(dwords_all, 0, 2 * DENSE_SET_WORDS * sizeof(unsigned)))) return st;
-        cs.wptr = dwords_all;
-    }
-    cs.wclean = false;
-    unsigned* const dcount = (unsigned*)dwords_all + cs.parity * DENSE_SET_WORDS;
-    unsigned* const dother = (unsigned*)dwords_all + (cs.parity ^ 1u) * DENSE_SET_WORDS;
-
-    const unsigned* fix_summary = nullptr;         // what a fix-up wave of k_tail looks at first (see exact_fixup_block)
-    unsigned fix_waves = 0;
-    if (per_item) {
-        fix_summary = g.force_general ? nullptr : (const unsigned*)ctab;
-        fix_waves = (unsigned)g.B;
-        unsigned* dwords = dcount;
-        auto go = [&](auto kern) {
-            // few items: big blocks (latency of the one item matters); many items: small blocks (they fill the chip) --
-            // down to ONE wave per item for ligand-sized items (a block's time is a chain of latencies whatever its
-            // size, and four times as many blocks are resident: cfg3's 32 768 items 343 -> ~90 us)
-            const long long avg = P.total_atoms / (long long)g.B;
-            const unsigned threads = (g.B < 512 && avg > 256) ? 1024u : (g.B >= 2048 && avg <= 64) ? 64u : (g.B >= 2048 && avg <= 128) ? 128u : 256u;
-            return be.launch(kern, dim3((unsigned)g.B), dim3(threads), g, P.coords, P.atom_offsets, P.sigmas, P.origins, P.box, P.affine,
-                             (unsigned*)start, (float4*)tpos, (uint2*)tidx, (uint2*)tcls, (float4*)rpos, (float4*)rw, (unsigned*)rcls,
-                             (unsigned*)ctab, dwords, (int*)eflag);
-        };
-        const int need = g.ncell + 1;
-        if (P.sigmas_f64) st = need <= 512 ? go(k_prepass_items<double, 512>) : need <= 2048 ? go(k_prepass_items<double, 2048>) : go(k_prepass_items<double, ITEM_HIST>);
-        else              st = need <= 512 ? go(k_prepass_items<float, 512>) : need <= 2048 ? go(k_prepass_items<float, 2048>) : go(k_prepass_items<float, ITEM_HIST>);
-        if (st) return st;
-    } else {
-        // The counters are zero when a call starts and every call leaves them zero (the scan kernels clear what they
-        // read): the memset -- a launch of its own, 6 us of a one-grid call -- is only
-        // needed for bytes no call has vouched for yet (a new or grown buffer, a call that failed half-way).
-        if (clean_after < count_bytes) {
-            if ((st = be.fill(count, 0, count_bytes))) return st;
-            clean_after = count_bytes;
-        }
-        const dim3 ablk(256), agrid((unsigned)ceil_div(P.total_atoms > 0 ? P.total_atoms : 1, 256));
-        const unsigned nblk = agrid.x, nfblk = (unsigned)ceil_div((long long)g.M, 256);
-        // behind a direct pass the chain is a fall-back that usually leaves at once: a few thousand workgroups that share
-        // the blocks instead of one each (k_bin_count, k_bin_fill)
-        const bool fallback_only = g.direct_words != nullptr && !solo;
-        const dim3 cgrid(fallback_only && nblk > 4096u ? 4096u : nblk);
-        const dim3 fgrid(fallback_only && nfblk > 4096u ? 4096u : nfblk);
-        const unsigned rows_per_block = 128;
-        const unsigned nl1 = (nblk + rows_per_block - 1) / rows_per_block;
-        void *bsets = nullptr, *l1sets = nullptr;
-        if ((st = be.ensure(WS_CLS_BLOCKS, (size_t)nblk * CLS_BLOCK_SET * sizeof(unsigned), &bsets, set))) return st;
-        if ((st = be.ensure(WS_CLS_L1, (size_t)nl1 * MERGE_SET * sizeof(unsigned), &l1sets, set))) return st;
-        fix_summary = g.force_general ? nullptr : (const unsigned*)bsets;
-        fix_waves = P.total_atoms > 0 ? nblk : 0u;
-        if (topo) {
-            // fix-up jobs per (item, WIDE atom of the molecule) -- the handle lists them -- or none at all.  (Round 5: one job per item;
-            // a wave then walked all of a 30 000-atom frame 64 atoms at a time and took its wide atoms one after the other.)
-            fix_summary = P.topo->wide_list;
-            const unsigned long long jobs = (unsigned long long)g.B * P.topo->n_wide;
-            if (jobs > 0xffffffffull) { err = "too many (item, wide atom) fix-up jobs (>= 2^32): split the batch"; return ST_EINVAL; }
-            fix_waves = (unsigned)jobs;
-        }
-        const unsigned* dfail = g.direct_words ? g.direct_words + DIRECT_FAILED : nullptr;
-        if (solo) {
-            st = P.sigmas_f64 ? be.launch(k_bin_solo<double>, agrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, (const double*)P.sigmas, P.origins,
-                                          P.affine, (unsigned*)dcnt, (float4*)rpos, (float4*)rw, (unsigned*)rcls, (uint2*)tcls, (unsigned*)ctab, (unsigned*)bsets)
-                              : be.launch(k_bin_solo<float>, agrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, (const float*)P.sigmas, P.origins,
-                                          P.affine, (unsigned*)dcnt, (float4*)rpos, (float4*)rw, (unsigned*)rcls, (uint2*)tcls, (unsigned*)ctab, (unsigned*)bsets);
-            if (st) return st;
-        } else {
-        if (g.direct_words) {
-            // the one-pass form first; the chain below is enqueued behind it and returns at once unless the pass gave up
-            st = P.sigmas_f64 ? be.launch(k_bin_direct<double>, agrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, (const double*)P.sigmas, P.origins,
-                                          P.affine, (unsigned*)dcnt, (float4*)rpos, (unsigned*)rcls, (uint2*)tcls, (const unsigned*)ctab, (unsigned*)bsets)
-                              : be.launch(k_bin_direct<float>, agrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, (const float*)P.sigmas, P.origins,
-                                          P.affine, (unsigned*)dcnt, (float4*)rpos, (unsigned*)rcls, (uint2*)tcls, (const unsigned*)ctab, (unsigned*)bsets);
-            if (st) return st;
-        }
-        if (P.total_atoms > 0) {
-            auto bin = [&](auto kern, auto* sig) {
-                return be.launch(kern, cgrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, sig, P.origins, P.box, P.affine,
-                                 (unsigned*)count, (float4*)tpos, (uint2*)tidx, (uint2*)tcls, (unsigned*)bsets, (int*)eflag, nblk);
-            };
-            if (topo) {                                      // (the ids stand where the sigmas would: bin_atom<.., TOPO>)
-                auto tbin = [&](auto kern) {
-                    return be.launch(kern, cgrid, ablk, g, P.coords, P.atom_offsets, P.total_atoms, (const float*)P.topo->ids, P.origins, P.box, P.affine,
-                                     (unsigned*)count, (float4*)tpos, (uint2*)tidx, (uint2*)tcls, (unsigned*)bsets, (int*)eflag, nblk);
-                };
-                st = g.pbc ? tbin(k_bin_count<float, 1, false, true>) : tbin(k_bin_count<float, 0, false, true>);
-            } else if (fallback_only) {                             // (open boundaries: the direct layouts have no periodic form)
-                st = P.sigmas_f64 ? bin(k_bin_count<double, 0, true>, (const double*)P.sigmas) : bin(k_bin_count<float, 0, true>, (const float*)P.sigmas);
-            } else if (P.sigmas_f64) st = g.pbc ? bin(k_bin_count<double, 1>, (const double*)P.sigmas) : bin(k_bin_count<double, 0>, (const double*)P.sigmas);
-            else              st = g.pbc ? bin(k_bin_count<float, 1>, (const float*)P.sigmas) : bin(k_bin_count<float, 0>, (const float*)P.sigmas);
-            if (st) return st;
-        }
-        // sigma classes (per-block sets -> class table) and the scan of the cell counts, fused two launches deep
-        const bool do_classes = P.total_atoms > 0 && !g.force_general && !topo;
-        if (!do_classes && !topo && (st = be.fill(ctab, 0xff, CLS_TABLE_WORDS * sizeof(unsigned)))) return st;   // nothing to register
-        if (!g.direct_words && ncells <= SMALL_PREPASS_MAX_CELLS && nblk <= SMALL_PREPASS_MAX_BLOCKS) {
-            // a small call (one grid): one launch instead of three dependent ones
-            if ((st = be.launch(k_prepass_small, dim3(1), dim3(SMALL_PREPASS_THREADS), (const unsigned*)bsets, do_classes ? nblk : 0u,
-                                (unsigned*)ctab, (unsigned*)count, (unsigned)ncells, (unsigned*)start))) return st;
-        } else {
-            const size_t nchunks = (ncells + 1 + SCAN_CHUNK - 1) / SCAN_CHUNK;
-            void* chunks = nullptr;
-            if ((st = be.ensure(WS_SCAN_CHUNKS, nchunks * sizeof(unsigned), &chunks, set))) return st;
-            const unsigned nl1_eff = do_classes ? nl1 : 0u;
-            if ((st = be.launch(k_prepass_reduce1, dim3(nl1_eff + (unsigned)nchunks), dim3(256), (const unsigned*)bsets, nblk, rows_per_block,
-                                nl1_eff, (unsigned*)l1sets, (const unsigned*)count, ncells, (unsigned*)chunks, dfail))) return st;
-            if ((st = be.launch(k_prepass_reduce2, dim3(do_classes ? 2u : 1u), dim3(256), (const unsigned*)l1sets, nl1_eff, (unsigned*)ctab,
-                                (unsigned*)chunks, (unsigned)nchunks, dfail))) return st;
-            if ((st = be.launch(k_scan_finish, dim3((unsigned)nchunks), dim3(SCAN_THREADS), (unsigned*)count, ncells,
-                                (const unsigned*)chunks, (unsigned*)start, dfail))) return st;
-        }
-        if (P.total_atoms > 0) {
-            // (FOUR temp slots per thread with their loads in flight together -- for calls that run alone on the chip, where the
-            //  48-register budget does not apply -- were measured: 261 us against 212, the pass is bound by its scattered
-            //  stores, not by the round trips in front of them)
-            auto fill = [&](auto kern, auto* sig) {
-                return be.launch(kern, fgrid, ablk, g, sig, (const unsigned*)start, (const float4*)tpos, (const uint2*)tidx, (const uint2*)tcls,
-                                 (float4*)rpos, (float4*)rw, (unsigned*)rcls, (const unsigned*)ctab, nfblk);
-            };
-            if (topo) st = fill(k_bin_fill<float, false, true>, (const float*)nullptr);
-            else if (fallback_only) st = P.sigmas_f64 ? fill(k_bin_fill<double, true>, (const double*)P.sigmas) : fill(k_bin_fill<float, true>, (const float*)P.sigmas);
-            else               st = P.sigmas_f64 ? fill(k_bin_fill<double>, (const double*)P.sigmas) : fill(k_bin_fill<float>, (const float*)P.sigmas);
-            if (st) return st;
-        }
-        }                                           // (not solo)
-    }
+    LatticeWorkspace W;
+    if ((st = acquire_lattice_workspace(be, P, L, g, set, W))) return st;
+    st = L.per_item() ? prepass_items(be, P, g, W) : L.solo() ? prepass_solo(be, P, g, W) : prepass_chain(be, P, L, g, W, set);
+    if (st) return st;
     be.prepass_done(set);
 
-    const dim3 tgrid(((total_tiles + 7u) / 8u) * 8u, (unsigned)g.G);
-    if ((unsigned long long)total_tiles * (unsigned)g.G > 0xFFFF0000ull) { err = "batch too large: more than 2^32 tiles x channel groups; split the batch"; return ST_EINVAL; }
-    void* dlist = nullptr;
-    if ((st = be.ensure(WS_DENSE_LIST, (size_t)total_tiles * g.G * sizeof(unsigned), &dlist, set))) return st;
+    const unsigned long long tile_waves = (unsigned long long)g.B * (unsigned)g.ntiles * (unsigned)g.G;
+    if (tile_waves > 0xFFFF0000ull) { err = "batch too large: more than 2^32 tiles x channel groups; split the batch"; return ST_EINVAL; }
+    if ((st = ensure_as(be, WS_DENSE_LIST, (size_t)tile_waves * sizeof(unsigned), W.dense_list, set))) return st;
     const int tier = choose_tier(P.lds_tier, be.feedback_host());
-    int flavour = team ? TILES_TEAM : (be.set_is_pipelined(set) ? TILES_LEAN : TILES_PLAIN);   // lean: leave registers for the next call's pre-pass
-    // many ligand-sized items (cfg3, cfg5): a workgroup per item sorts its entries once for all its tiles
-    if (P.tile_items != 0 && ((P.tile_items > 0 && !team) || (P.tile_items < 0 && P.tile_team <= 0 && per_item && P.total_atoms <= 96LL * (long long)g.B && g.ntiles <= 512)))
-        flavour = TILES_ITEMS;
-    TailArgs ta;
-    // (the general path has no dense tiles; its fix-up waves still run, and its statistics stay what they were)
-    ta.dense_wgs = g.force_general ? 0u : (total_tiles * (unsigned)g.G < 4096u ? total_tiles * (unsigned)g.G : 4096u);
-    ta.fix_jobs = fix_waves;
-    ta.fix_waves = fix_waves < 8192u ? fix_waves : 8192u;         // (the fix-up waves share the jobs: see k_tail)
-    ta.other_words = dother; ta.per_item = topo ? 2 : per_item ? 1 : 0; ta.summary = fix_summary; ta.P = &P; ta.tcls = topo ? (const void*)P.topo->cw : tcls;
-    if (topo) { ctab = const_cast<unsigned*>(P.topo->table); ta.sigmas = P.topo->sigmas; ta.sigmas_f64 = P.topo->sigmas_f64; }
-    ta.team_waves = (P.tile_team == 4 || P.tile_team == 8 || P.tile_team == 16) ? P.tile_team : 0;
-    if (solo) { ta.solo_counts = (unsigned*)dcnt; ta.solo_n = (unsigned)(DIRECT_HEAD + (ncells << g.cnt_shift)); }
-    if (topo && g.topo_wide != 0u && P.seq == 0u && !g.force_general && P.exact_redo_list >= 0) {
-        // a trajectory of a molecule with wide sigmas (ions): the exact recomputes of k_tail's hits are spread over many waves (k_exact_redo)
-        void* rl = nullptr;
-        if ((st = be.ensure(WS_REDO_LIST, (size_t)(REDO_HEAD + (size_t)REDO_CAP * REDO_ENTRY) * sizeof(unsigned), &rl, set))) return st;
+    // a topology call: the tile kernels read the handle's table (nobody writes through it: k_tail's table is a solo call's)
+    if (L.topo()) W.cls_table = const_cast<unsigned*>(P.topo->table);
+    if (L.split_exact_fixup) {
+        if ((st = ensure_as(be, WS_REDO_LIST, (size_t)(REDO_HEAD + (size_t)REDO_CAP * REDO_ENTRY) * sizeof(unsigned), W.redo_list, set))) return st;
         // (the list's counter back to zero: queued behind the previous call's k_exact_redo on this stream, in front of this call's hot kernels)
-        if ((st = be.launch(k_zero_words, dim3(1), dim3(WAVE), (unsigned*)rl, (unsigned)REDO_HEAD))) return st;
-        ta.redo_list = (unsigned*)rl;
-        ta.redo_cap = P.exact_redo_list > 0 && (unsigned)P.exact_redo_list < REDO_CAP ? (unsigned)P.exact_redo_list : REDO_CAP;   // (a tiny list: tests of the overflow pass)
+        if ((st = be.launch(k_zero_words, dim3(1), dim3(WAVE), W.redo_list, (unsigned)REDO_HEAD))) return st;
     }
-    be.hot_begin(flavour, g.K, ECAP_TIER[tier]);
-    st = g.K == 8 ? launch_tiles<8>(be, tier, flavour, tgrid, ta, g, start, rpos, rw, rcls, ctab, P.out, dcount, dlist, eflag)
-                  : launch_tiles<4>(be, tier, flavour, tgrid, ta, g, start, rpos, rw, rcls, ctab, P.out, dcount, dlist, eflag);
+    be.hot_begin(L.flavour, g.K, ECAP_TIER[tier]);
+    st = g.K == 8 ? launch_tiles<8>(be, tier, P, L, g, W) : launch_tiles<4>(be, tier, P, L, g, W);
     be.hot_end();
+    const bool tail_ran = L.dense_wgs + L.fix_waves != 0u;
     if (!st) {
-        cs.clean = clean_after;
+        CounterState& cs = *W.cs;
+        cs.clean = W.clean_after;
         cs.wclean = true;
-        cs.tptr = topo ? table_before : ctab;       // every pre-pass leaves a whole table in the buffer (a topology call: untouched)
-        if (solo) cs.dclean = dbytes;               // k_tail has zeroed them
-        if (ta.dense_wgs + ta.fix_waves != 0u) cs.parity ^= 1u;       // k_tail has cleared the other copy: the next call's
+        cs.tptr = L.topo() ? W.table_before : W.cls_table;       // every pre-pass leaves a whole table in the buffer (a topology call: untouched)
+        if (L.solo()) cs.dclean = W.direct_bytes;                // k_tail has zeroed them
+        if (tail_ran) cs.parity ^= 1u;                           // k_tail has cleared the other copy: the next call's
     }
-    be.note_error_flag_mirrored(!st && !g.force_general && ta.dense_wgs != 0u && be.feedback_dev() != nullptr);
-    be.note_tail_reports(!st && !g.force_general && ta.dense_wgs + ta.fix_waves != 0u && be.feedback_dev() != nullptr && P.seq != 0u);
+    const bool tail_mirrors = !st && !g.force_general && be.feedback_dev() != nullptr;
+    be.note_error_flag_mirrored(tail_mirrors && L.dense_wgs != 0u);
+    be.note_tail_reports(tail_mirrors && tail_ran && P.seq != 0u);
     be.tile_done(set);
     return st;
 }
@@ -655,21 +689,19 @@ int run_topology_build(BE& be, const void* d_sigmas, int sigmas_f64, long long n
     const int G = ceil_div(C, CHG);
     const double w_scale = voxelsize * voxelsize, R = CUTOFF_A / voxelsize;
     const float w_exact_max = (float)(7.647 / (R * R));                     // plan_lattice's rule
-    const unsigned nblk = (unsigned)ceil_div(n, 256), rows_per_block = 128, nl1 = (nblk + rows_per_block - 1) / rows_per_block;
-    void *bsets = nullptr, *l1sets = nullptr;
+    const unsigned nblk = (unsigned)ceil_div(n, 256), nl1 = (unsigned)ceil_div(nblk, CLS_ROWS_PER_BLOCK);
+    unsigned *bsets = nullptr, *l1sets = nullptr;
     int st;
-    if ((st = be.ensure(WS_CLS_BLOCKS, (size_t)nblk * CLS_BLOCK_SET * sizeof(unsigned), &bsets, 0))) return st;
-    if ((st = be.ensure(WS_CLS_L1, (size_t)nl1 * MERGE_SET * sizeof(unsigned), &l1sets, 0))) return st;
-    st = sigmas_f64 ? be.launch(k_topology_classes<double>, dim3(nblk), dim3(256), (const double*)d_sigmas, n, C, G, w_scale, cw, (unsigned*)bsets)
-                    : be.launch(k_topology_classes<float>, dim3(nblk), dim3(256), (const float*)d_sigmas, n, C, G, w_scale, cw, (unsigned*)bsets);
-    if (st) return st;
-    if ((st = be.launch(k_merge_classes, dim3(nl1), dim3(256), (const unsigned*)bsets, nblk, (unsigned)CLS_BLOCK_SET, rows_per_block,
-                        (unsigned*)l1sets, (unsigned*)nullptr))) return st;
-    if ((st = be.launch(k_merge_classes, dim3(1), dim3(256), (const unsigned*)l1sets, nl1, (unsigned)MERGE_SET, nl1, (unsigned*)nullptr, table))) return st;
-    return sigmas_f64 ? be.launch(k_topology_ids<double>, dim3(nblk), dim3(256), (const double*)d_sigmas, (const uint2*)cw, (const unsigned*)table, n, C, G,
-                                  w_scale, w_exact_max, ids, flags, wide_list)
-                      : be.launch(k_topology_ids<float>, dim3(nblk), dim3(256), (const float*)d_sigmas, (const uint2*)cw, (const unsigned*)table, n, C, G,
-                                  w_scale, w_exact_max, ids, flags, wide_list);
+    if ((st = ensure_as(be, WS_CLS_BLOCKS, (size_t)nblk * CLS_BLOCK_SET * sizeof(unsigned), bsets, 0))) return st;
+    if ((st = ensure_as(be, WS_CLS_L1, (size_t)nl1 * MERGE_SET * sizeof(unsigned), l1sets, 0))) return st;
+    return with_sigmas(d_sigmas, sigmas_f64, [&](auto* sig) {
+        using S = sigma_of<decltype(sig)>;
+        int s;
+        if ((s = be.launch(k_topology_classes<S>, dim3(nblk), dim3(256), sig, n, C, G, w_scale, cw, bsets))) return s;
+        if ((s = be.launch(k_merge_classes, dim3(nl1), dim3(256), bsets, nblk, (unsigned)CLS_BLOCK_SET, CLS_ROWS_PER_BLOCK, l1sets, (unsigned*)nullptr))) return s;
+        if ((s = be.launch(k_merge_classes, dim3(1), dim3(256), l1sets, nl1, (unsigned)MERGE_SET, nl1, (unsigned*)nullptr, table))) return s;
+        return be.launch(k_topology_ids<S>, dim3(nblk), dim3(256), sig, cw, table, n, C, G, w_scale, w_exact_max, ids, flags, wide_list);
+    });
 }
 
 // Explicit centres: sigma -> w, then the brute-force double-precision kernel.
@@ -684,13 +716,13 @@ int run_centers(BE& be, const double* d_centers, long long V, const float* d_coo
         for (int ax = 0; ax < 3; ++ax)
             if (!(box_host[ax] > 2.0 * CUTOFF_A)) { err = "periodic box edges must be > 10 A (2 x cutoff)"; return ST_EBOX; }
     const int G = ceil_div(C, CHG);
-    void* w = nullptr;
-    int st = be.ensure(WS_W_EXPLICIT, (size_t)(N > 0 ? N : 1) * sizeof(float4) * 2 * G, &w, 0);
+    float4* w = nullptr;
+    int st = ensure_as(be, WS_W_EXPLICIT, (size_t)(N > 0 ? N : 1) * sizeof(float4) * 2 * G, w, 0);
     if (st) return st;
     if (N > 0) {
-        const dim3 blk(256), grid((unsigned)ceil_div(N, 256));
-        st = sigmas_f64 ? be.launch(k_sigma_to_w<double>, grid, blk, (const double*)d_sigmas, N, C, G, 1.0, (float4*)w)
-                        : be.launch(k_sigma_to_w<float>, grid, blk, (const float*)d_sigmas, N, C, G, 1.0, (float4*)w);
+        st = with_sigmas(d_sigmas, sigmas_f64, [&](auto* sig) {
+            return be.launch(k_sigma_to_w<sigma_of<decltype(sig)>>, dim3((unsigned)ceil_div(N, 256)), dim3(256), sig, N, C, G, 1.0, w);
+        });
         if (st) return st;
     }
     // 64 centres per workgroup; its waves split the atoms: as many (4, 8, 16) as it takes to put ~4 waves on every SIMD
@@ -698,7 +730,7 @@ int run_centers(BE& be, const double* d_centers, long long V, const float* d_coo
     int waves = 4;
     while (waves < EXPL_MAX_WAVES && wgs * waves < 4096) waves *= 2;
     const dim3 grid((unsigned)ceil_div(V, EXPL_CENTERS), (unsigned)G), blk((unsigned)(waves * WAVE));
-    return be.launch(k_occupancy_centers, grid, blk, d_centers, V, d_coords, N, (const float4*)w, C,
+    return be.launch(k_occupancy_centers, grid, blk, d_centers, V, d_coords, N, w, C,
                      box_host ? 1 : 0, box_host ? box_host[0] : 0.0, box_host ? box_host[1] : 0.0,
                      box_host ? box_host[2] : 0.0, d_out);
 }

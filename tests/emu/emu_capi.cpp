@@ -11,7 +11,10 @@
 #include <cstring>
 #include <string>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
+#include <cxxabi.h>
+#include <dlfcn.h>
 
 using namespace mkamd;
 
@@ -76,6 +79,132 @@ struct EmuBackend {
 };
 
 thread_local std::string g_err;
+
+// ---- the launch recorder: run_lattice's host side alone ----
+// A backend that RUNS nothing: it writes down every ensure / fill / launch (kernel instantiation, grid, block, every argument)
+// and every hook run_lattice calls, so that a CPU test can pin WHICH path a call takes (all paths compute the same bits, so
+// the value tests cannot see it).  Workspace buffers and the problem's arrays are address ranges that nothing ever
+// dereferences; a pointer argument is written as the range it points into plus its byte offset.
+struct RecBackend {
+    struct Range { uintptr_t base; size_t bytes; std::string name; };
+    std::vector<Range> ranges;
+    uintptr_t next_base = (uintptr_t)1 << 32;
+    void* bufs[2][WS_NSLOTS] = {};
+    size_t caps[2][WS_NSLOTS] = {};
+    int gens[2][WS_NSLOTS] = {};
+    unsigned feedback[FEEDBACK_WORDS] = {};
+    CounterState counters[2];
+    bool can_pipeline = false, piped = false;
+    int next_set = 0;
+    std::string out, last_grid;
+    char line[1024];
+
+    void* range(const std::string& name, size_t bytes)
+    {
+        const uintptr_t base = next_base;
+        next_base += (bytes + 2 * 4096) & ~(uintptr_t)4095;
+        ranges.push_back(Range{base, bytes, name});
+        return (void*)base;
+    }
+    std::string where(const void* p) const
+    {
+        if (!p) return "null";
+        const uintptr_t a = (uintptr_t)p;
+        for (auto r = ranges.rbegin(); r != ranges.rend(); ++r)
+            if (a >= r->base && a <= r->base + r->bytes) return a == r->base ? r->name : r->name + "+" + std::to_string(a - r->base);
+        return "unknown";
+    }
+    CounterState& counter_state(int set) { return counters[set & 1]; }
+    void note_error_flag_mirrored(bool yes) { out += yes ? "  error flag mirrored\n" : ""; }
+    void note_tail_reports(bool yes) { out += yes ? "  tail reports\n" : ""; }
+    const volatile unsigned* feedback_host() const { return feedback; }
+    unsigned* feedback_dev() { return fb_dev; }
+    unsigned* fb_dev = (unsigned*)range("fb", FEEDBACK_WORDS * sizeof(unsigned));
+    int ensure(int slot, size_t bytes, void** ptr, int set = 0)
+    {
+        snprintf(line, sizeof line, "  ensure slot %d set %d bytes %zu\n", slot, set, bytes);
+        out += line;
+        if (bytes == 0) bytes = 16;
+        if (caps[set][slot] < bytes) {                       // grow-only, a new buffer is a new address
+            snprintf(line, sizeof line, "w%d.%d#%d", slot, set, ++gens[set][slot]);
+            bufs[set][slot] = range(line, bytes);
+            caps[set][slot] = bytes;
+        }
+        *ptr = bufs[set][slot];
+        return 0;
+    }
+    int fill(void* p, int byte, size_t bytes)
+    {
+        snprintf(line, sizeof line, "  fill %s byte %d bytes %zu\n", where(p).c_str(), byte, bytes);
+        out += line;
+        return 0;
+    }
+    void arg(const GridDesc& g)
+    {
+        snprintf(line, sizeof line, "grid{n %d %d %d t %d %d %d %d K %d cs %d %d h %d nc %d %d %d %d cstride %d cls_per_item %d rint %d C %d G %d B %d pbc %d "
+                 "general %d R2 %.9g %.9g inv_res %.17g w_scale %.17g Rp %.17g V %lld M %u img_cap %d hurry %d res %.17g w_exact_max %.9g reach_tau %.9g "
+                 "cell_cap %d spill %u %u cnt_shift %d topo %lld %u direct_words ",
+                 g.nx, g.ny, g.nz, g.tnx, g.tny, g.tnz, g.ntiles, g.K, g.cs_log2, g.cs, g.h, g.ncx, g.ncy, g.ncz, g.ncell, g.cstride, g.cls_per_item, g.rint,
+                 g.C, g.G, g.B, g.pbc, g.force_general, g.R2, g.R2cull, g.inv_res, g.w_scale, g.Rp, g.V, g.M, g.img_cap, g.prepass_hurry, g.res,
+                 g.w_exact_max, g.reach_tau, g.cell_cap, g.spill_base, g.spill_cap, g.cnt_shift, g.topo_n, g.topo_wide);
+        const std::string full = line + where(g.direct_words) + "}";
+        out += full == last_grid ? std::string("grid") : full;        // (in full where it differs from the one written last)
+        last_grid = full;
+    }
+    template <class T> void arg(T* p) { out += where((const void*)p); }
+    template <class T> std::enable_if_t<std::is_arithmetic<T>::value> arg(T v)
+    {
+        if (std::is_floating_point<T>::value) snprintf(line, sizeof line, "%.17g", (double)v);
+        else if (std::is_signed<T>::value) snprintf(line, sizeof line, "%lld", (long long)v);
+        else snprintf(line, sizeof line, "%llu", (unsigned long long)v);
+        out += line;
+    }
+    template <class... KA, class... A>
+    int launch(void (*kernel)(KA...), dim3 grid, dim3 block, A... args)
+    {
+        // the instantiation's name: the library's own dynamic symbol at the kernel's address, without the parameter list
+        Dl_info info;
+        std::string name = "unknown";
+        if (dladdr((void*)kernel, &info) && info.dli_sname && info.dli_saddr == (void*)kernel) {
+            int st = 0;
+            char* d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &st);
+            name = d && !st ? d : info.dli_sname;
+            free(d);
+            if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);
+            const size_t paren = name.find('(');
+            if (paren != std::string::npos) name.erase(paren);
+        }
+        snprintf(line, sizeof line, "  launch %s grid %u %u %u block %u %u %u :", name.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z);
+        out += line;
+        ((out += ' ', arg((KA)args)), ...);                  // (as the kernel's parameter types: what the launch converts them to)
+        out += '\n';
+        return 0;
+    }
+    void hot_begin(int flavour, int K, int ecap) { snprintf(line, sizeof line, "  hot_begin flavour %d K %d ecap %d\n", flavour, K, ecap); out += line; }
+    void hot_end() { out += "  hot_end\n"; }
+    int acquire_set(bool big_enough)                         // (as mkamd_ctx::acquire_set: the sets alternate between pipelined calls)
+    {
+        piped = big_enough && can_pipeline;
+        const int set = piped ? next_set : 0;
+        if (piped) next_set ^= 1;
+        snprintf(line, sizeof line, "  acquire_set %d -> set %d\n", (int)big_enough, set);
+        out += line;
+        return set;
+    }
+    bool set_is_pipelined(int) const { return piped; }
+    bool pipelining_possible() const { return can_pipeline; }
+    void prepass_done(int set) { snprintf(line, sizeof line, "  prepass_done %d\n", set); out += line; }
+    void tile_done(int set) { snprintf(line, sizeof line, "  tile_done %d\n", set); out += line; piped = false; }
+    void counters_line(int set)
+    {
+        const CounterState& c = counters[set & 1];
+        snprintf(line, sizeof line, "  counters set %d: %s clean %zu, words %s clean %d parity %u, direct %s clean %zu, table %s\n", set & 1, where(c.ptr).c_str(),
+                 c.clean, where(c.wptr).c_str(), (int)c.wclean, c.parity, where(c.dptr).c_str(), c.dclean, where(c.tptr).c_str());
+        out += line;
+    }
+};
+
+thread_local std::string g_trace;
 
 }  // namespace
 
@@ -248,6 +377,50 @@ int emu_plan(int B, long long total_atoms, int C, const int* nvox, double voxels
     memcpy(out_ints, v, sizeof v);
     return 0;
 }
+
+// run_lattice on the recorder above -> what it asked of its backend, as text (emu_trace_text()).
+// iv: B, total_atoms, C, sigmas_f64, nvox[3], pbc, max_images, tile_k, force_general, lds_tier, prepass_mode, fine_cells, direct, cell_cap, spill_cap,
+//     seq, tile_team, tile_items, exact_redo_list, topology (0 none, 1 a handle), its n_wide, its overflow flag, pipelining possible, calls on one
+//     backend, feedback words [NTIER + 1];   dv: voxelsize, value_tol
+int emu_trace_lattice(const long long* iv, const double* dv)
+{
+    RecBackend be;
+    LatticeProblem P;
+    int i = 0;
+    P.B = (int)iv[i++]; P.total_atoms = iv[i++]; P.C = (int)iv[i++]; P.sigmas_f64 = (int)iv[i++];
+    P.nvox[0] = (int)iv[i++]; P.nvox[1] = (int)iv[i++]; P.nvox[2] = (int)iv[i++];
+    P.pbc = (int)iv[i++]; P.max_images = (int)iv[i++]; P.tile_k = (int)iv[i++]; P.force_general = (int)iv[i++]; P.lds_tier = (int)iv[i++];
+    P.prepass_mode = (int)iv[i++]; P.fine_cells = (int)iv[i++]; P.direct = (int)iv[i++]; P.cell_cap = (int)iv[i++]; P.spill_cap = (unsigned)iv[i++];
+    P.seq = (unsigned)iv[i++]; P.tile_team = (int)iv[i++]; P.tile_items = (int)iv[i++]; P.exact_redo_list = (int)iv[i++];
+    const bool topo = iv[i++] != 0;
+    TopologyDev T;
+    T.n_wide = (unsigned)iv[i++]; T.overflow = iv[i++] != 0;
+    be.can_pipeline = iv[i++] != 0;
+    const int calls = (int)iv[i++];
+    for (int t = 0; t <= NTIER; ++t) be.feedback[t] = (unsigned)iv[i++];
+    P.voxelsize = dv[0]; P.value_tol = dv[1];
+    const size_t big = (size_t)1 << 40;
+    P.coords = (const float*)be.range("coords", big); P.atom_offsets = (const long long*)be.range("offsets", big);
+    P.sigmas = topo ? nullptr : be.range("sigmas", big); P.origins = (const double*)be.range("origins", big);
+    P.box = P.pbc ? (const float*)be.range("box", big) : nullptr; P.affine = nullptr; P.out = (float*)be.range("out", big);
+    if (topo) {
+        T.n = P.B > 0 ? P.total_atoms / P.B : 0; T.C = P.C; T.G = ceil_div(P.C, CHG); T.sigmas_f64 = P.sigmas_f64; T.voxelsize = P.voxelsize;
+        T.ids = (const unsigned*)be.range("topo.ids", big); T.cw = (const uint2*)be.range("topo.cw", big); T.sigmas = be.range("topo.sigmas", big);
+        T.table = (const unsigned*)be.range("topo.table", big); T.wide = T.n_wide != 0u; T.wide_list = (const unsigned*)be.range("topo.wide_list", big);
+        P.topo = &T;
+    }
+    int st = 0;
+    for (int c = 0; c < calls && !st; ++c) {
+        be.out += "call " + std::to_string(c) + "\n";
+        st = run_lattice(be, P, g_err);
+        be.out += "  status " + std::to_string(st) + (st ? ": " + g_err : std::string()) + "\n";
+        be.counters_line(0);
+        if (be.can_pipeline) be.counters_line(1);
+    }
+    g_trace = be.out;
+    return st;
+}
+const char* emu_trace_text(void) { return g_trace.c_str(); }
 
 // ---- distance_utils row: same launch sequences on host memory ----
 int emu_dist_trajectory(const float* coords, long long F, const float* box, const unsigned* sel1, long long n1,

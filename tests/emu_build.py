@@ -29,7 +29,7 @@ def build(force=False):
         subprocess.check_call(
             ["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
              "-Wno-unused-variable", "-Wno-unknown-pragmas", "-ffp-contract=off",
-             os.path.join(_EMU, "emu_capi.cpp"), "-o", _LIB])
+             os.path.join(_EMU, "emu_capi.cpp"), "-o", _LIB, "-ldl"])
     return _LIB
 
 
@@ -40,6 +40,7 @@ def lib():
         _lib = ctypes.CDLL(_LIB)
         _lib.emu_last_error.restype = ctypes.c_char_p
         _lib.emu_last_dist_kernel.restype = ctypes.c_char_p
+        _lib.emu_trace_text.restype = ctypes.c_char_p
     return _lib
 
 
@@ -150,6 +151,25 @@ def plan(B, total_atoms, C, nvox, voxelsize, pbc=0, max_images=1, tile_k=0):
         raise RuntimeError(f"emu status {st}: {lib().emu_last_error().decode()}")
     keys = ["K", "tnx", "tny", "tnz", "ntiles", "cs", "h", "ncx", "ncy", "ncz", "ncell", "rint", "G", "M"]
     return dict(zip(keys, out.tolist()))
+
+
+_TRACE_KEYS = ["B", "total_atoms", "C", "sigmas_f64", "nx", "ny", "nz", "pbc", "max_images", "tile_k", "force_general", "lds_tier", "prepass_mode",
+               "fine_cells", "direct", "cell_cap", "spill_cap", "seq", "tile_team", "tile_items", "exact_redo_list", "topo", "topo_wide",
+               "topo_overflow", "pipelining", "calls"]
+_TRACE_DEFAULTS = dict(B=1, total_atoms=0, C=8, sigmas_f64=0, nx=24, ny=24, nz=24, pbc=0, max_images=1, tile_k=0, force_general=0, lds_tier=-1,
+                       prepass_mode=-1, fine_cells=0, direct=-1, cell_cap=0, spill_cap=0, seq=0, tile_team=-1, tile_items=-1, exact_redo_list=0,
+                       topo=0, topo_wide=0, topo_overflow=0, pipelining=0, calls=1)
+
+
+def trace_lattice(voxelsize=1.0, value_tol=0.0, feedback=(0, 0, 0, 0), **problem):
+    """run_lattice's host side alone, on a backend that records instead of running (emu_capi.cpp, RecBackend): the fields of a
+    LatticeProblem (and of the recorder: a topology handle, `pipelining` possible, `calls` on one backend, the tier `feedback`
+    of the call before) -> (status, the trace: every ensure / fill / launch with its kernel instantiation, geometry and arguments)."""
+    unknown = set(problem) - set(_TRACE_KEYS)
+    assert not unknown, unknown
+    iv = np.array([{**_TRACE_DEFAULTS, **problem}[k] for k in _TRACE_KEYS] + list(feedback), np.int64)
+    st = lib().emu_trace_lattice(_p(iv), _p(np.array([voxelsize, value_tol], np.float64)))
+    return st, lib().emu_trace_text().decode()
 
 
 # ---- distance_utils row ---------------------------------------------------------------------------
