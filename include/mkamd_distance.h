@@ -162,6 +162,30 @@ int mkamd_align_host(mkamd_ctx* ctx, float* coords, int64_t n_atoms, int64_t n_f
                      int64_t n_ref_frames, const uint32_t* sel, const uint32_t* refsel, int64_t n_sel, const int64_t* frames,
                      int64_t n_list, int64_t refframe, int matchingframes);
 
+/* ---- surface area: the solvent-accessible surface of every frame (Shrake-Rupley; moleculekit projections/metricsasa.py, which
+ * calls mdtraj's sasa.cpp) ----
+ * Per frame and per atom i whose mask is non-zero: R_i = radii[i] (probe included); the neighbours of i are all j != i with
+ * |x_i - x_j|^2 < (R_i + R_j)^2; of the n_points sphere points p = x_i + R_i s (the reference's golden-section spiral) the ones
+ * with |p - x_j|^2 < R_j^2 for no neighbour j are counted, and area_i = ((float32(4 pi / n_points) * count) * R_i) * R_i is added
+ * to out[frame, atom_mapping[i]].  Every atom shields, selected or not.  All of it in float32 with separate multiplies and adds
+ * (|d|^2 = (dx dx + dy dy) + dz dz): the count is the reference's exactly.  Coordinates are divided by `coord_div` first (IEEE
+ * division; 10: Angstrom in, the reference's nanometres inside -- radii are then nanometres and the areas square nanometres;
+ * 1: as they are).  atom_mapping int32: inside [0, n_out) and NON-DECREASING (the atoms of a column are contiguous; a column's
+ * areas are added one after the other in atom order, no floating-point atomics: the same bits on every run); mask int32.
+ * out [n_frames, n_out] float32 is filled by the caller; columns no selected atom maps to are left alone.
+ * Refused with MKAMD_EINVAL, nothing added to out: two atoms with r^2 < 1e-10 in the divided coordinates (the reference aborts
+ * the process there), a mapping value out of range or smaller than its predecessor.  Both calls return after the kernels have
+ * finished (the refusal flag is read back). */
+
+/* device arrays: d_xyz frame-major [n_frames, n_atoms, 3] (the XTC decoder's and the voxelizer's items), on the context's stream */
+int mkamd_sasa_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, int64_t n_frames, const float* d_radii, int32_t n_points,
+                   const int32_t* d_atom_mapping, const int32_t* d_mask, float coord_div, float* d_out, int64_t n_out);
+/* host arrays: coords [n_atoms, 3, n_frames] (Molecule.coords); keep uint32 [n_keep] lists the atoms of the system (NULL: all
+ * n_atoms) -- only their rows are uploaded; radii, atom_mapping and mask are [n_keep], in the order of keep. */
+int mkamd_sasa_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const uint32_t* keep, int64_t n_keep,
+                    const float* radii, int32_t n_points, const int32_t* atom_mapping, const int32_t* mask, float coord_div,
+                    float* out, int64_t n_out);
+
 #ifdef __cplusplus
 }
 #endif

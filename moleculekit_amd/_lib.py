@@ -115,6 +115,9 @@ SIGNATURES = {
     "mkamd_align_rmsd_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_int, _vp,
                                       _vp]),
     "mkamd_align_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_int]),
+    # include/mkamd_distance.h, surface area
+    "mkamd_sasa_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i32, _vp, _vp, ctypes.c_float, _vp, _c_i64]),
+    "mkamd_sasa_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i32, _vp, _vp, ctypes.c_float, _vp, _c_i64]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@
 #include "pipeline.h"
 #include "dist_pipeline.h"
 #include "align_pipeline.h"
+#include "sasa_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "cpu_occupancy.h"
@@ -2021,6 +2022,68 @@ try {
         for (int64_t i = 0; i < K; ++i) dst[frames[i]] = src[frames[i]];
     }
     return MKAMD_OK;
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// surface area (include/mkamd_distance.h "surface area"; sasa_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+static mkamd::SasaArgs sasa_args(const float* d_xyz, int64_t N, int64_t F, const float* d_radii, int32_t n_points, const int32_t* d_mapping,
+                                 const int32_t* d_mask, float coord_div, float* d_out, int64_t n_out)
+{
+    mkamd::SasaArgs a;
+    a.xyz = d_xyz; a.n_atoms = N; a.n_frames = F; a.radii = d_radii; a.n_points = n_points;
+    a.mapping = reinterpret_cast<const int*>(d_mapping); a.mask = reinterpret_cast<const int*>(d_mask);
+    a.n_out = n_out; a.coord_div = coord_div; a.out = d_out;
+    return a;
+}
+
+extern "C" int mkamd_sasa_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const float* d_radii, int32_t n_points,
+                              const int32_t* d_mapping, const int32_t* d_mask, float coord_div, float* d_out, int64_t n_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N > 0 && F > 0 && (!d_xyz || !d_radii || !d_mapping || !d_mask || !d_out)) return fail(MKAMD_EINVAL, "NULL pointer");
+    std::string err;
+    st = mkamd::run_sasa(*ctx, sasa_args(d_xyz, N, F, d_radii, n_points, d_mapping, d_mask, coord_div, d_out, n_out), err);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_sasa_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* keep, int64_t n_keep,
+                               const float* radii, int32_t n_points, const int32_t* mapping, const int32_t* mask, float coord_div,
+                               float* out, int64_t n_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || n_keep < 0 || n_out < 0) return fail(MKAMD_EINVAL, "negative size");
+    const int64_t n = keep ? n_keep : N;
+    if (n == 0 || F == 0) return MKAMD_OK;
+    if (!coords || !radii || !mapping || !mask || !out) return fail(MKAMD_EINVAL, "NULL pointer");
+    for (int64_t k = 0; keep && k < n; ++k)
+        if ((int64_t)keep[k] >= N) return fail(MKAMD_EINVAL, "kept atom index out of range");
+    if (n_out < 1) return fail(MKAMD_EINVAL, "n_out must be at least 1");
+    // the kept atoms' rows of [N][3][F] -> [3 n][F] -> frame-major [F][n][3] on the device
+    const size_t row = (size_t)3 * (size_t)F;
+    const float* src = coords;
+    if (keep) {
+        std::vector<float>& pk = ctx->packed_coords;
+        if (pk.size() < (size_t)n * row) pk.resize((size_t)n * row);
+        for (int64_t k = 0; k < n; ++k) std::memcpy(pk.data() + (size_t)k * row, coords + (size_t)keep[k] * row, row * sizeof(float));
+        src = pk.data();
+    }
+    void *dslab, *dxyz, *drad, *dmap, *dmask, *dout;
+    if ((st = upload(ctx, WS_S_SLAB, src, (size_t)n * row * 4, &dslab))) return st;
+    if ((st = ctx->ensure(WS_S_XYZ, (size_t)n * row * 4, &dxyz))) return st;
+    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dslab, 3 * n, F, F, 1.0f, (float*)dxyz))) return st;
+    if ((st = upload(ctx, WS_S_RADII, radii, (size_t)n * 4, &drad))) return st;
+    if ((st = upload(ctx, WS_S_MAP, mapping, (size_t)n * 4, &dmap))) return st;
+    if ((st = upload(ctx, WS_S_MASK, mask, (size_t)n * 4, &dmask))) return st;
+    if ((st = upload(ctx, WS_S_OUT, out, (size_t)F * n_out * 4, &dout))) return st;
+    std::string err;
+    st = mkamd::run_sasa(*ctx, sasa_args((const float*)dxyz, n, F, (const float*)drad, n_points, (const int32_t*)dmap, (const int32_t*)dmask,
+                                         coord_div, (float*)dout, n_out), err);
+    if (st) return err.empty() ? st : fail(st, err);
+    return ctx->to_host(out, dout, (size_t)F * n_out * 4);
 } MK_API_CATCH
 
 #ifdef MK_PHASE_TIMERS

@@ -42,6 +42,8 @@ enum WsSlot {
     WS_D_G2A, WS_D_G2O, WS_D_MASS, WS_D_CNT, WS_D_TOT, WS_D_BASE, WS_D_CONTACTS, WS_D_MASK,
     // alignment (align_pipeline.h) and its host entry point
     WS_A_REFPART, WS_A_PART, WS_A_RPART, WS_A_FOLD, WS_A_REFFOLD, WS_A_SLAB, WS_A_XYZ, WS_A_REF, WS_A_SEL, WS_A_REFSEL, WS_A_FRAMES, WS_A_AFFINE,
+    // surface area (sasa_pipeline.h) and its host entry point
+    WS_S_POINTS, WS_S_PACK, WS_S_AREA, WS_S_ERR, WS_S_SLAB, WS_S_XYZ, WS_S_RADII, WS_S_MAP, WS_S_MASK, WS_S_OUT,
     WS_NSLOTS
 };
 
