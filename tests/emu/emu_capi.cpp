@@ -381,7 +381,7 @@ int emu_plan(int B, long long total_atoms, int C, const int* nvox, double voxels
 // run_lattice on the recorder above -> what it asked of its backend, as text (emu_trace_text()).
 // iv: B, total_atoms, C, sigmas_f64, nvox[3], pbc, max_images, tile_k, force_general, lds_tier, prepass_mode, fine_cells, direct, cell_cap, spill_cap,
 //     seq, tile_team, tile_items, exact_redo_list, topology (0 none, 1 a handle), its n_wide, its overflow flag, pipelining possible, calls on one
-//     backend, feedback words [NTIER + 1];   dv: voxelsize, value_tol
+//     backend, feedback words [NTIER + 1], an affine present (0 / 1);   dv: voxelsize, value_tol
 int emu_trace_lattice(const long long* iv, const double* dv)
 {
     RecBackend be;
@@ -398,11 +398,13 @@ int emu_trace_lattice(const long long* iv, const double* dv)
     be.can_pipeline = iv[i++] != 0;
     const int calls = (int)iv[i++];
     for (int t = 0; t <= NTIER; ++t) be.feedback[t] = (unsigned)iv[i++];
+    const bool with_affine = iv[i++] != 0;
     P.voxelsize = dv[0]; P.value_tol = dv[1];
     const size_t big = (size_t)1 << 40;
     P.coords = (const float*)be.range("coords", big); P.atom_offsets = (const long long*)be.range("offsets", big);
     P.sigmas = topo ? nullptr : be.range("sigmas", big); P.origins = (const double*)be.range("origins", big);
-    P.box = P.pbc ? (const float*)be.range("box", big) : nullptr; P.affine = nullptr; P.out = (float*)be.range("out", big);
+    P.box = P.pbc ? (const float*)be.range("box", big) : nullptr; P.affine = with_affine ? (const double*)be.range("affine", big) : nullptr;
+    P.out = (float*)be.range("out", big);
     if (topo) {
         T.n = P.B > 0 ? P.total_atoms / P.B : 0; T.C = P.C; T.G = ceil_div(P.C, CHG); T.sigmas_f64 = P.sigmas_f64; T.voxelsize = P.voxelsize;
         T.ids = (const unsigned*)be.range("topo.ids", big); T.cw = (const uint2*)be.range("topo.cw", big); T.sigmas = be.range("topo.sigmas", big);

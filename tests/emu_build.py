@@ -161,13 +161,13 @@ _TRACE_DEFAULTS = dict(B=1, total_atoms=0, C=8, sigmas_f64=0, nx=24, ny=24, nz=2
                        topo=0, topo_wide=0, topo_overflow=0, pipelining=0, calls=1)
 
 
-def trace_lattice(voxelsize=1.0, value_tol=0.0, feedback=(0, 0, 0, 0), **problem):
+def trace_lattice(voxelsize=1.0, value_tol=0.0, feedback=(0, 0, 0, 0), affine=0, **problem):
     """run_lattice's host side alone, on a backend that records instead of running (emu_capi.cpp, RecBackend): the fields of a
     LatticeProblem (and of the recorder: a topology handle, `pipelining` possible, `calls` on one backend, the tier `feedback`
-    of the call before) -> (status, the trace: every ensure / fill / launch with its kernel instantiation, geometry and arguments)."""
+    of the call before, `affine` = 1: the call carries per-item transforms, written "affine" where a launch is handed them) -> (status, the trace: every ensure / fill / launch with its kernel instantiation, geometry and arguments)."""
     unknown = set(problem) - set(_TRACE_KEYS)
     assert not unknown, unknown
-    iv = np.array([{**_TRACE_DEFAULTS, **problem}[k] for k in _TRACE_KEYS] + list(feedback), np.int64)
+    iv = np.array([{**_TRACE_DEFAULTS, **problem}[k] for k in _TRACE_KEYS] + list(feedback) + [int(affine)], np.int64)
     st = lib().emu_trace_lattice(_p(iv), _p(np.array([voxelsize, value_tol], np.float64)))
     return st, lib().emu_trace_text().decode()
 

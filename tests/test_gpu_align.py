@@ -178,3 +178,45 @@ def test_aligned_xtc_stream_equals_aligned_then_voxelized(hip_ctx):
         worst = max(worst, float(np.abs(streamed[f].cpu().numpy() - exp).max()))
     print(f"aligned stream vs oracle: {worst:.2e}")
     assert worst <= TOL
+
+
+@pytest.mark.parametrize("ions", [0, 5])
+def test_aligned_xtc_stream_with_getchannels_shaped_sigmas(hip_ctx, ions):
+    """The case above draws thousands of distinct sigmas, which no topology handle takes (at most 15): its streams fall back to the
+    repeated sigma matrix.  A getChannels-shaped matrix -- 8 channels, the atom's radius where a property holds, a handful of
+    distinct values, with and without ions -- is what production passes: the handle is built (checked here directly), so the
+    aligned stream runs the topology binning and, with ions, the split exact fix-up."""
+    import torch
+    from moleculekit_amd import _lib, align, batch, xtc
+    from oracle import oracle
+    from tests.synth import synth_sigmas
+    g = np.load(GOLDEN)
+    ca = g["rmsd_ca_idx"]
+    dev = torch.device("cuda", hip_ctx.device)
+    frames = np.arange(40)
+    xyz, _, _, _ = xtc.read_xtc_frames_dev(XTC, frames, scale=10.0, ctx=hip_ctx)
+    N = int(xyz.shape[1])
+    sig = synth_sigmas(np.random.default_rng(3), N).astype(np.float32)
+    if ions:
+        at = np.linspace(0, N - 1, ions).astype(int)
+        sig[at] = 0.0
+        sig[at, 7] = 2.27
+    assert len(np.unique(sig[sig != 0])) <= 15
+    topo = _lib.Topology(hip_ctx, sig, 1.0)
+    assert topo.has_wide_sigmas == bool(ions)
+    topo.close()
+    ref = xyz[0, ca].cpu().numpy()
+    center = ref.astype(np.float64).mean(0)
+    box = [16, 16, 16]
+    streamed = torch.cat([f for _, f in batch.iterVoxelizeXTC(XTC, sig, center, box, 1.0, pbc=False, frames=frames, chunk=16,
+                                                               ctx=hip_ctx, align=(ref, ca))])
+    aligned = align.align_trajectory(xyz, torch.as_tensor(ref, device=dev), ca, np.arange(len(ca)), ctx=hip_ctx)
+    coords = aligned.permute(1, 2, 0).contiguous()
+    direct = torch.cat([f for _, f in batch.iterVoxelizeTrajectory(coords, sig, center, box, 1.0, chunk=16, ctx=hip_ctx)])
+    torch.cuda.synchronize()
+    assert torch.equal(streamed, direct)
+    a = aligned.cpu().numpy()
+    centers = oracle.grid_centers(center - 8.0, np.array(box), 1.0)
+    worst = max(float(np.abs(streamed[f].cpu().numpy() - oracle.calculate_occupancy(centers, a[f], sig)).max()) for f in (0, 17, 39))
+    print(f"aligned stream, getChannels-shaped sigmas, {ions} ions: {worst:.2e}")
+    assert worst <= TOL
