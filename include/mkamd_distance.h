@@ -186,6 +186,27 @@ int mkamd_sasa_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_
                     const float* radii, int32_t n_points, const int32_t* atom_mapping, const int32_t* mask, float coord_div,
                     float* out, int64_t n_out);
 
+/* ---- shell counts: how many atoms of sel2 lie in each of n_edges - 1 concentric shells around every atom of sel1, per frame
+ * (moleculekit projections/metricshell.py) -- without the [n_frames, n1 * n2] distance matrix the reference histograms ----
+ * Layouts of the distance row: coords [n_atoms, 3, n_frames], box [3, n_frames], sel1 / sel2 / digitized_chains uint32.  For frame
+ * f, centre i and atom j: d2 = the squared float32 minimum-image distance of dist_trajectory (the image shift where pbc is set and
+ * digitized_chains[sel1[i]] != digitized_chains[sel2[j]]), and counts[f, i, s] = #{ j : T[s] < d2 <= T[s + 1] } with the
+ * non-decreasing float32 thresholds T = d2_thresholds [n_edges] (+inf allowed; a NaN d2 is in no shell).  The thresholds are on the
+ * SQUARED distance: for a shell edge e, T is the largest float32 whose correctly rounded root is <= e, and then d2 <= T is exactly
+ * fl32(sqrt(d2)) <= e (the rounded root is monotone) -- moleculekit_amd.shell.shell_thresholds computes them.  symmetric: sel1 and
+ * sel2 are the same list (n1 == n2) and the pair (i, i) is left out.  counts int32 [n_frames, n1, n_edges - 1] is cleared by the
+ * call; integer sums: the same on every run.  n_edges 2 .. 33 (1 .. 32 shells), n_frames < 2^30; else MKAMD_EINVAL.  No workspace
+ * proportional to n1 * n2 exists anywhere. */
+
+/* device arrays, asynchronous on the context's stream; d2_thresholds is HOST memory, read before the call returns */
+int mkamd_shell_counts_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t n_frames, const float* d_box,
+                           const uint32_t* d_sel1, int64_t n1, const uint32_t* d_sel2, int64_t n2, const uint32_t* d_digitized_chains,
+                           int symmetric, int pbc, const float* d2_thresholds, int64_t n_edges, int32_t* d_counts);
+/* host arrays: only the selected atoms' rows are uploaded (as the other host forms do); returns when counts is filled */
+int mkamd_shell_counts_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const float* box,
+                            const uint32_t* sel1, int64_t n1, const uint32_t* sel2, int64_t n2, const uint32_t* digitized_chains,
+                            int symmetric, int pbc, const float* d2_thresholds, int64_t n_edges, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 #include "dist_pipeline.h"
 #include "align_pipeline.h"
 #include "sasa_pipeline.h"
+#include "shell_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "cpu_occupancy.h"
@@ -686,7 +687,7 @@ try {
 int mkamd_ctx_set_dist_kernels(mkamd_ctx* ctx, int avoid_mask)
 try {
     if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
-    if (avoid_mask < 0 || avoid_mask > 255) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel)");
+    if (avoid_mask < 0 || avoid_mask > 1023) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel), 256 / 512 (shell counts: not the frame-lane / not the atom-lane kernel)");
     ctx->dist_avoid = avoid_mask;
     return MKAMD_OK;
 } MK_API_CATCH
@@ -2084,6 +2085,67 @@ try {
                                          coord_div, (float*)dout, n_out), err);
     if (st) return err.empty() ? st : fail(st, err);
     return ctx->to_host(out, dout, (size_t)F * n_out * 4);
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// shell counts (include/mkamd_distance.h "shell counts"; shell_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_shell_counts_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t F, const float* d_box, const uint32_t* d_sel1,
+                                      int64_t n1, const uint32_t* d_sel2, int64_t n2, const uint32_t* d_chains, int symmetric, int pbc,
+                                      const float* d2_thresholds, int64_t n_edges, int32_t* d_counts)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (n_atoms < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (F > 0 && n1 > 0 && (!d_coords || !d_box || !d_sel1 || (n2 > 0 && !d_sel2) || !d_chains || !d_counts)) return fail(MKAMD_EINVAL, "NULL pointer");
+    std::string err;
+    st = mkamd::run_shell_counts(*ctx, d_coords, F, d_box, d_sel1, n1, d_sel2, n2, d_chains, symmetric, pbc, d2_thresholds, n_edges,
+                                 reinterpret_cast<int*>(d_counts), err, (ctx->dist_avoid >> 8) & 3);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_shell_counts_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const float* box, const uint32_t* sel1, int64_t n1,
+                                       const uint32_t* sel2, int64_t n2, const uint32_t* chains, int symmetric, int pbc,
+                                       const float* d2_thresholds, int64_t n_edges, int32_t* counts)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || n1 < 0 || n2 < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (n_edges < 2 || n_edges > mkamd::SH_MAX_EDGES) return fail(MKAMD_EINVAL, "numshells must be between 1 and 32 (n_edges between 2 and 33)");
+    if (F == 0 || n1 == 0) {
+        if (!d2_thresholds) return fail(MKAMD_EINVAL, "NULL pointer");
+        return MKAMD_OK;
+    }
+    if (!coords || !box || !sel1 || (n2 > 0 && !sel2) || !chains || !d2_thresholds || !counts) return fail(MKAMD_EINVAL, "NULL pointer");
+    for (int64_t i = 0; i < n1; ++i) if (sel1[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel1 index out of range");
+    for (int64_t i = 0; i < n2; ++i) if (sel2[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel2 index out of range");
+    void *dc, *db, *d1, *d2, *dch, *dout;
+    // only the selected atoms' rows go up when they are few (host_pack.h); the selections and chain ids in the packed numbering
+    mkamd::PackedAtoms pk;
+    pk.collect(sel1, n1); pk.collect(sel2, n2);
+    int64_t rows = N;
+    if (!(ctx->dist_avoid & 32) && pk.finish(coords, N, F, ctx->packed_coords)) {
+        const std::vector<uint32_t> p1 = pk.remap(sel1, n1), p2 = pk.remap(sel2, n2), pc = pk.gather(chains);
+        rows = pk.size();
+        if ((st = upload(ctx, WS_H_COORDS, ctx->packed_coords.data(), (size_t)rows * 3 * F * 4, &dc))) return st;
+        if ((st = upload(ctx, WS_D_SEL1, p1.data(), (size_t)n1 * 4, &d1))) return st;
+        if ((st = upload(ctx, WS_D_SEL2, p2.data(), (size_t)n2 * 4, &d2))) return st;
+        if ((st = upload(ctx, WS_D_CHAINS, pc.data(), (size_t)rows * 4, &dch))) return st;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporaries above are read by then)
+    } else {
+        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)N * 3 * F * 4, &dc))) return st;
+        if ((st = upload(ctx, WS_D_SEL1, sel1, (size_t)n1 * 4, &d1))) return st;
+        if ((st = upload(ctx, WS_D_SEL2, sel2, (size_t)n2 * 4, &d2))) return st;
+        if ((st = upload(ctx, WS_D_CHAINS, chains, (size_t)N * 4, &dch))) return st;
+    }
+    if ((st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
+    const size_t bytes = (size_t)F * (size_t)n1 * (size_t)(n_edges - 1) * 4;
+    if ((st = ctx->ensure(WS_H_OUT, bytes, &dout, 0))) return st;
+    st = mkamd_shell_counts_dev(ctx, (const float*)dc, rows, F, (const float*)db, (const uint32_t*)d1, n1, (const uint32_t*)d2, n2,
+                                (const uint32_t*)dch, symmetric, pbc, d2_thresholds, n_edges, (int32_t*)dout);
+    if (st) return st;
+    return ctx->to_host(counts, dout, bytes);
 } MK_API_CATCH
 
 #ifdef MK_PHASE_TIMERS
