@@ -106,6 +106,7 @@ int mkamd_selftest_sqrt(mkamd_ctx* ctx, uint64_t* mismatches, uint32_t* first_ba
  * of the selected atoms' rows (csrc/host_pack.h); 64: selfdist calls keep the pair-table kernel where the triangular form of the row kernel
  * would be taken (selections of >= 700 atoms up to 32 frames, of >= 1 500 atoms at any frame count).  128: rectangular calls of few frames whose rows are too short for the row kernel and whose first selection is long keep the tile
  * kernel instead of the row kernel with the selections swapped (lanes along the first selection, transposed stores).
+ * 256 / 512: shell counts do not take their frame-lane / atom-lane kernel; 1024 / 2048: the dihedral angles the same.
  * Calls of at most 32 frames take the row kernel wherever it applies (its lanes
  * run along the second atoms; the other kernels' along frames).  Every kernel produces the same
  * bits; for tests (every kernel over the same shapes) and same-box A-B timing. */
@@ -206,6 +207,29 @@ int mkamd_shell_counts_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atom
 int mkamd_shell_counts_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const float* box,
                             const uint32_t* sel1, int64_t n1, const uint32_t* sel2, int64_t n2, const uint32_t* digitized_chains,
                             int symmetric, int pbc, const float* d2_thresholds, int64_t n_edges, int32_t* counts);
+
+/* ---- dihedral angles: the torsion of n_dihedrals atom quadruples in every frame (moleculekit projections/metricdihedral.py:
+ * _calcDihedralAngles -> dihedral.py:dihedralAngle) ----
+ * coords [n_atoms, 3, n_frames] float32, quads uint32 [n_dihedrals, 4] (indices < n_atoms), box [3, n_frames] float32 or NULL (then
+ * n_box_frames is not read; else it must equal n_frames).  For atoms x0..x3: r12 = x0 - x1, r23 = x1 - x2, r34 = x2 - x3 -- with a
+ * box each component once through the reference's _wrapBondedDistance (< -box / 2: + box; > box / 2: - box; a box of zeros changes
+ * nothing) --, c1 = r23 x r34, c2 = r12 x r23, p1 = (r12 . c1) * sqrt(r23 . r23), p2 = c1 . c2: the reference's float32 operations
+ * in its order, no fused multiply-add, the root correctly rounded -- (p1, p2) are its bits.  The angle is -atan2(p1, p2).  `mode`:
+ *   MKAMD_DIH_TERMS 0    out [n_frames, n_dihedrals, 2]   (p1, p2)
+ *   MKAMD_DIH_RADIANS 1  out [n_frames, n_dihedrals]      the float64 atan2 of the terms, rounded once to float32
+ *   MKAMD_DIH_DEGREES 2  out [n_frames, n_dihedrals]      the same times 180 / pi in float64, rounded once
+ *   MKAMD_DIH_SINCOS 3   out [n_frames, 2 n_dihedrals]    sin, cos interleaved: (-p1, p2) / sqrt(p1^2 + p2^2) in float64, rounded once
+ * p1 = p2 = 0 (collinear atoms): angle 0, sin 0, cos 1.  A NaN coordinate gives NaN in every output of that (frame, dihedral) only.
+ * MKAMD_EINVAL: an unknown mode, a NULL pointer, n_box_frames != n_frames, n_frames or n_dihedrals >= 2^30, (host form) an index
+ * >= n_atoms.  No workspace proportional to n_frames * n_dihedrals besides the result. */
+enum { MKAMD_DIH_TERMS = 0, MKAMD_DIH_RADIANS = 1, MKAMD_DIH_DEGREES = 2, MKAMD_DIH_SINCOS = 3 };
+
+/* device arrays, asynchronous on the context's stream; the indices are NOT checked (they are device memory) */
+int mkamd_dihedrals_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t n_frames, const float* d_box, int64_t n_box_frames,
+                        const uint32_t* d_quads, int64_t n_dihedrals, int mode, float* d_out);
+/* host arrays: only the rows of the atoms the quads name are uploaded (as the other host forms do); returns when out is filled */
+int mkamd_dihedrals_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const float* box, int64_t n_box_frames,
+                         const uint32_t* quads, int64_t n_dihedrals, int mode, float* out);
 
 #ifdef __cplusplus
 }

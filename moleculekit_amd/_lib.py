@@ -121,6 +121,9 @@ SIGNATURES = {
     # include/mkamd_distance.h, shell counts
     "mkamd_shell_counts_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _c_int, _vp, _c_i64, _vp]),
     "mkamd_shell_counts_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _c_int, _vp, _c_i64, _vp]),
+    # include/mkamd_distance.h, dihedral angles
+    "mkamd_dihedrals_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _vp]),
+    "mkamd_dihedrals_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, _c_int, _vp]),
 }
 
 _lib = None
@@ -353,7 +356,7 @@ class Context:
     def set_dist_kernels(self, avoid_mask: int = 0):
         """Kernels dist_trajectory must NOT take (include/mkamd_distance.h): 1 block-per-frame, 2 rows, 4 rectangular tiles, 8 the
         row kernel's 16-byte stores; 16: the row kernel wherever it applies; 32: host calls upload the whole coordinate array (no packing
-        of the selected atoms' rows); 64: selfdist calls keep the pair-table kernel (no triangular row kernel); 128: short-row calls of few frames keep the tile kernel (no swapped row kernel); 256 / 512: shell counts avoid their frame-lane / atom-lane kernel; 0 = free choice.  Same bits whichever runs (tests, A-B timing)."""
+        of the selected atoms' rows); 64: selfdist calls keep the pair-table kernel (no triangular row kernel); 128: short-row calls of few frames keep the tile kernel (no swapped row kernel); 256 / 512: shell counts avoid their frame-lane / atom-lane kernel; 1024 / 2048: dihedrals the same; 0 = free choice.  Same bits whichever runs (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_dist_kernels(self._h, int(avoid_mask)))
 
     def set_reduction_block(self, block: int = 0):

@@ -12,6 +12,7 @@
 #include "align_pipeline.h"
 #include "sasa_pipeline.h"
 #include "shell_pipeline.h"
+#include "dihedral_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "cpu_occupancy.h"
@@ -687,7 +688,7 @@ try {
 int mkamd_ctx_set_dist_kernels(mkamd_ctx* ctx, int avoid_mask)
 try {
     if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
-    if (avoid_mask < 0 || avoid_mask > 1023) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel), 256 / 512 (shell counts: not the frame-lane / not the atom-lane kernel)");
+    if (avoid_mask < 0 || avoid_mask > 4095) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel), 256 / 512 (shell counts: not the frame-lane / not the atom-lane kernel), 1024 / 2048 (dihedrals: the same)");
     ctx->dist_avoid = avoid_mask;
     return MKAMD_OK;
 } MK_API_CATCH
@@ -2146,6 +2147,61 @@ try {
                                 (const uint32_t*)dch, symmetric, pbc, d2_thresholds, n_edges, (int32_t*)dout);
     if (st) return st;
     return ctx->to_host(counts, dout, bytes);
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// dihedral angles (include/mkamd_distance.h "dihedral angles"; dihedral_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_dihedrals_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t F, const float* d_box, int64_t n_box_frames,
+                                   const uint32_t* d_quads, int64_t D, int mode, float* d_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (n_atoms < 0 || F < 0 || D < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (d_box && n_box_frames != F) return fail(MKAMD_EINVAL, "box must be [3, n_frames]: n_box_frames differs from n_frames");
+    if (F > 0 && D > 0 && (!d_coords || !d_quads || !d_out)) return fail(MKAMD_EINVAL, "NULL pointer");
+    std::string err;
+    st = mkamd::run_dihedrals(*ctx, d_coords, F, d_box, d_box != nullptr, d_quads, D, mode, d_out, err, (ctx->dist_avoid >> 10) & 3);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_dihedrals_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const float* box, int64_t n_box_frames,
+                                    const uint32_t* quads, int64_t D, int mode, float* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || D < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (mode < mkamd::DIH_TERMS || mode > mkamd::DIH_SINCOS) return fail(MKAMD_EINVAL, "mode must be 0 (terms), 1 (radians), 2 (degrees) or 3 (sincos)");
+    if (box && n_box_frames != F) return fail(MKAMD_EINVAL, "box must be [3, n_frames]: n_box_frames differs from n_frames");
+    if (F == 0 || D == 0) return MKAMD_OK;
+    if (!coords || !quads || !out) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (F > 0x3fffffffLL || D > 0x3fffffffLL || (double)F * (double)D * (double)mkamd::dih_width(mode) >= 1.0e18) return fail(MKAMD_EINVAL, "result too large");
+    for (int64_t i = 0; i < 4 * D; ++i) if (quads[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "quads: atom index out of range");
+    // the reference wraps only where the box is not all zeros (dihedral.py:dihedralAngle)
+    bool wrap = false;
+    if (box) for (int64_t i = 0; i < 3 * F && !wrap; ++i) wrap = !(box[i] == 0.0f);
+    void *dc, *db = nullptr, *dq, *dout;
+    // only the rows of the atoms the quads name go up when they are few (host_pack.h); the quads in the packed numbering
+    mkamd::PackedAtoms pk;
+    pk.collect(quads, 4 * D);
+    int64_t rows = N;
+    if (!(ctx->dist_avoid & 32) && pk.finish(coords, N, F, ctx->packed_coords)) {
+        const std::vector<uint32_t> pq = pk.remap(quads, 4 * D);
+        rows = pk.size();
+        if ((st = upload(ctx, WS_H_COORDS, ctx->packed_coords.data(), (size_t)rows * 3 * F * 4, &dc))) return st;
+        if ((st = upload(ctx, WS_D_SEL1, pq.data(), (size_t)D * 16, &dq))) return st;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporary above is read by then)
+    } else {
+        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)N * 3 * F * 4, &dc))) return st;
+        if ((st = upload(ctx, WS_D_SEL1, quads, (size_t)D * 16, &dq))) return st;
+    }
+    if (wrap && (st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
+    const size_t bytes = (size_t)F * (size_t)D * (size_t)mkamd::dih_width(mode) * 4;
+    if ((st = ctx->ensure(WS_H_OUT, bytes, &dout, 0))) return st;
+    st = mkamd_dihedrals_dev(ctx, (const float*)dc, rows, F, (const float*)db, F, (const uint32_t*)dq, D, mode, (float*)dout);
+    if (st) return st;
+    return ctx->to_host(out, dout, bytes);
 } MK_API_CATCH
 
 #ifdef MK_PHASE_TIMERS
