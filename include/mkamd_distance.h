@@ -107,6 +107,7 @@ int mkamd_selftest_sqrt(mkamd_ctx* ctx, uint64_t* mismatches, uint32_t* first_ba
  * would be taken (selections of >= 700 atoms up to 32 frames, of >= 1 500 atoms at any frame count).  128: rectangular calls of few frames whose rows are too short for the row kernel and whose first selection is long keep the tile
  * kernel instead of the row kernel with the selections swapped (lanes along the first selection, transposed stores).
  * 256 / 512: shell counts do not take their frame-lane / atom-lane kernel; 1024 / 2048: the dihedral angles the same.
+ * 4096 / 8192: the group moments do not take the form in which a lane group owns a whole (frame, group) / the segmented form.
  * Calls of at most 32 frames take the row kernel wherever it applies (its lanes
  * run along the second atoms; the other kernels' along frames).  Every kernel produces the same
  * bits; for tests (every kernel over the same shapes) and same-box A-B timing. */
@@ -230,6 +231,45 @@ int mkamd_dihedrals_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, 
 /* host arrays: only the rows of the atoms the quads name are uploaded (as the other host forms do); returns when out is filled */
 int mkamd_dihedrals_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const float* box, int64_t n_box_frames,
                          const uint32_t* quads, int64_t n_dihedrals, int mode, float* out);
+
+/* ---- group moments: weighted first and second moments of small sets of atoms in every frame, optionally after each frame's rigid
+ * transform (moleculekit projections/metriccoordinate.py, metricgyration.py, metricsphericalcoordinate.py, metricfluctuation.py) ----
+ * Device layout: frame-major float32 d_xyz [n_frames, n_atoms, 3] (the alignment's).  d_affine float64 [n_frames, 12] or NULL: what
+ * mkamd_align_transforms_dev writes for frames 0 .. n_frames - 1; every gathered atom is then float32(R x + t) first -- the bits
+ * mkamd_align_apply_dev would have stored, and the aligned trajectory is never written.  Groups are CSR: atoms uint32 [n_sel]
+ * (indices < n_atoms), offsets uint32 [n_groups + 1] (offsets[0] = 0, offsets[n_groups] = n_sel, no empty group), weights float32
+ * [n_sel] or NULL (1).  max_group: the largest group's size (it shapes the launch only).  Per (frame, group) everything is summed in
+ * double, in a fixed order, without floating-point atomics: the same bits on every run.  `mode`:
+ *   MKAMD_MOM_CENTER 0     out float32 [n_frames, 3 n_groups], column c * n_groups + g:  sum w x_c / sum w, rounded once
+ *   MKAMD_MOM_GYRATION 1   out float32 [n_frames, n_groups, 4]: sqrt(sum w q / sum w) for q = |r|^2, r_y^2 + r_z^2, r_x^2 + r_z^2,
+ *                          r_x^2 + r_y^2 with r = x - (centre of mass), the centre kept in double; rounded once
+ *   MKAMD_MOM_SPHERICAL 2  exactly two unweighted groups (target, reference): d = centroid_0 - centroid_1 in double,
+ *                          out float32 [n_frames, 3] = (|d|, acos(d_z / |d|), atan2(d_y, d_x)); |d| = 0 gives NaN for the second
+ *   MKAMD_MOM_FLUCT 3      (mkamd_fluctuation_*) out FLOAT64 [n_frames, n_sel] = sum_c (x_c - ref_c)^2 per listed atom, or with
+ *                          offsets [n_frames, n_groups]: its unweighted mean over each group's atoms.  ref float64 [n_sel, 3], or NULL:
+ *                          the mean over all frames of the (transformed) positions, computed first in double in a fixed order
+ * MKAMD_EINVAL: an unknown mode, a NULL pointer, n_frames, n_groups or n_sel >= 2^30, the spherical mode with other than two groups or with
+ * weights, (host forms) an index >= n_atoms, an empty group, offsets that do not start at 0 or decrease. */
+enum { MKAMD_MOM_CENTER = 0, MKAMD_MOM_GYRATION = 1, MKAMD_MOM_SPHERICAL = 2, MKAMD_MOM_FLUCT = 3 };
+
+/* device arrays, asynchronous on the context's stream; indices and offsets are NOT checked (they are device memory) */
+int mkamd_group_moments_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, int64_t n_frames, const double* d_affine,
+                            const uint32_t* d_atoms, const uint32_t* d_offsets, const float* d_weights, int64_t n_groups, int64_t n_sel,
+                            int64_t max_group, int mode, float* d_out);
+/* d_offsets NULL: per atom (n_groups and max_group are not read); d_ref NULL: the mean over the frames */
+int mkamd_fluctuation_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, int64_t n_frames, const double* d_affine,
+                          const uint32_t* d_atoms, int64_t n_sel, const uint32_t* d_offsets, int64_t n_groups, int64_t max_group,
+                          const double* d_ref, double* d_out);
+/* host arrays: coords float32 [n_atoms, 3, n_frames] (Molecule.coords).  alnsel uint32 [n_aln] with alnref float32 [n_aln, 3], or
+ * NULL: every frame is first superposed (mkamd_align_transforms_dev) with its atoms alnsel on the positions alnref.  Only the rows of
+ * the atoms that atoms and alnsel name are packed and uploaded; returns when out is filled. */
+int mkamd_group_moments_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const uint32_t* alnsel,
+                             const float* alnref, int64_t n_aln, const uint32_t* atoms, const uint32_t* offsets, const float* weights,
+                             int64_t n_groups, int mode, float* out);
+/* ref float64 [n_sel, 3] or NULL (the mean over the frames); offsets NULL: per atom */
+int mkamd_fluctuation_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const uint32_t* alnsel,
+                           const float* alnref, int64_t n_aln, const uint32_t* atoms, int64_t n_sel, const uint32_t* offsets,
+                           int64_t n_groups, const double* ref, double* out);
 
 #ifdef __cplusplus
 }

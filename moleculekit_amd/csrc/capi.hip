@@ -13,6 +13,7 @@
 #include "sasa_pipeline.h"
 #include "shell_pipeline.h"
 #include "dihedral_pipeline.h"
+#include "moments_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "cpu_occupancy.h"
@@ -688,7 +689,7 @@ try {
 int mkamd_ctx_set_dist_kernels(mkamd_ctx* ctx, int avoid_mask)
 try {
     if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
-    if (avoid_mask < 0 || avoid_mask > 4095) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel), 256 / 512 (shell counts: not the frame-lane / not the atom-lane kernel), 1024 / 2048 (dihedrals: the same)");
+    if (avoid_mask < 0 || avoid_mask > 16383) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel), 256 / 512 (shell counts: not the frame-lane / not the atom-lane kernel), 1024 / 2048 (dihedrals: the same), 4096 / 8192 (group moments: not the form in which a lane group owns a (frame, group) / not the segmented form)");
     ctx->dist_avoid = avoid_mask;
     return MKAMD_OK;
 } MK_API_CATCH
@@ -2200,6 +2201,150 @@ try {
     const size_t bytes = (size_t)F * (size_t)D * (size_t)mkamd::dih_width(mode) * 4;
     if ((st = ctx->ensure(WS_H_OUT, bytes, &dout, 0))) return st;
     st = mkamd_dihedrals_dev(ctx, (const float*)dc, rows, F, (const float*)db, F, (const uint32_t*)dq, D, mode, (float*)dout);
+    if (st) return st;
+    return ctx->to_host(out, dout, bytes);
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// group moments (include/mkamd_distance.h "group moments"; moments_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+static mkamd::MomArgs mom_args(const float* d_xyz, int64_t N, int64_t F, const double* d_affine, const uint32_t* d_atoms, const uint32_t* d_offsets,
+                               const float* d_weights, int64_t G, int64_t n_sel, int64_t max_group)
+{
+    mkamd::MomArgs a;
+    a.xyz = d_xyz; a.n_atoms = N; a.n_frames = F; a.affine = d_affine;
+    a.atoms = d_atoms; a.offsets = d_offsets; a.weights = d_weights;
+    a.n_groups = G; a.n_sel = n_sel; a.max_group = max_group;
+    return a;
+}
+
+extern "C" int mkamd_group_moments_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const double* d_affine, const uint32_t* d_atoms,
+                                       const uint32_t* d_offsets, const float* d_weights, int64_t G, int64_t n_sel, int64_t max_group, int mode,
+                                       float* d_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    std::string err;
+    st = mkamd::run_group_moments(*ctx, mom_args(d_xyz, N, F, d_affine, d_atoms, d_offsets, d_weights, G, n_sel, max_group), mode, d_out, err,
+                                  (ctx->dist_avoid >> 12) & 3);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_fluctuation_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const double* d_affine, const uint32_t* d_atoms,
+                                     int64_t n_sel, const uint32_t* d_offsets, int64_t G, int64_t max_group, const double* d_ref, double* d_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    std::string err;
+    st = mkamd::run_fluctuation(*ctx, mom_args(d_xyz, N, F, d_affine, d_atoms, d_offsets, nullptr, d_offsets ? G : 0, n_sel, d_offsets ? max_group : 1),
+                                d_ref, d_out, err, (ctx->dist_avoid >> 12) & 3);
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+// What the two host forms share: the rows of the atoms that `atoms` and `alnsel` name, packed ([M, 3, F]), uploaded and transposed to
+// frame-major [F, M, 3]; the lists in the packed numbering; each frame's transform onto alnref where an alignment is asked for.
+struct MomHostInputs {
+    void *dxyz = nullptr, *datoms = nullptr, *doffs = nullptr, *dw = nullptr, *daff = nullptr;
+    int64_t rows = 0, max_group = 1;
+};
+
+static int mom_host_inputs(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* alnsel, const float* alnref, int64_t n_aln,
+                           const uint32_t* atoms, int64_t n_sel, const uint32_t* offsets, int64_t G, const float* weights, MomHostInputs& in)
+{
+    int st;
+    if (!coords || !atoms || (alnsel && !alnref)) return fail(MKAMD_EINVAL, "NULL pointer");
+    for (int64_t k = 0; k < n_sel; ++k) if (atoms[k] >= (uint64_t)N) return fail(MKAMD_EINVAL, "atoms: atom index out of range");
+    for (int64_t k = 0; alnsel && k < n_aln; ++k) if (alnsel[k] >= (uint64_t)N) return fail(MKAMD_EINVAL, "alnsel: atom index out of range");
+    if (offsets) {
+        if (offsets[0] != 0 || (int64_t)offsets[G] != n_sel) return fail(MKAMD_EINVAL, "offsets must start at 0 and end at the number of group atoms");
+        for (int64_t g = 0; g < G; ++g) {
+            if (offsets[g + 1] <= offsets[g]) return fail(MKAMD_EINVAL, "an empty group (or decreasing offsets)");
+            in.max_group = std::max<int64_t>(in.max_group, (int64_t)offsets[g + 1] - (int64_t)offsets[g]);
+        }
+    }
+    mkamd::PackedAtoms pk;
+    pk.collect(atoms, n_sel);
+    if (alnsel) pk.collect(alnsel, n_aln);
+    std::sort(pk.uniq.begin(), pk.uniq.end());
+    pk.uniq.erase(std::unique(pk.uniq.begin(), pk.uniq.end()), pk.uniq.end());
+    const int64_t M = pk.size();
+    const size_t row = (size_t)3 * (size_t)F;
+    std::vector<float>& pc = ctx->packed_coords;
+    if (pc.size() < (size_t)M * row) pc.resize((size_t)M * row);
+    for (int64_t k = 0; k < M; ++k) std::memcpy(pc.data() + (size_t)k * row, coords + (size_t)pk.uniq[(size_t)k] * row, row * sizeof(float));
+    in.rows = M;
+    void* dslab;
+    if ((st = upload(ctx, WS_A_SLAB, pc.data(), (size_t)M * row * 4, &dslab))) return st;
+    if ((st = ctx->ensure(WS_A_XYZ, (size_t)M * row * 4, &in.dxyz))) return st;
+    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dslab, 3 * M, F, F, 1.0f, (float*)in.dxyz))) return st;
+    const std::vector<uint32_t> pa = pk.remap(atoms, n_sel);
+    if ((st = upload(ctx, WS_M_ATOMS, pa.data(), (size_t)n_sel * 4, &in.datoms))) return st;
+    if (offsets && (st = upload(ctx, WS_M_OFFS, offsets, (size_t)(G + 1) * 4, &in.doffs))) return st;
+    if (weights && (st = upload(ctx, WS_M_W, weights, (size_t)n_sel * 4, &in.dw))) return st;
+    if (alnsel) {
+        const std::vector<uint32_t> ps = pk.remap(alnsel, n_aln);
+        std::vector<uint32_t> rs((size_t)n_aln);
+        for (int64_t k = 0; k < n_aln; ++k) rs[(size_t)k] = (uint32_t)k;
+        void *dsel, *drefsel, *dref;
+        if ((st = upload(ctx, WS_A_SEL, ps.data(), (size_t)n_aln * 4, &dsel))) return st;
+        if ((st = upload(ctx, WS_A_REFSEL, rs.data(), (size_t)n_aln * 4, &drefsel))) return st;
+        if ((st = upload(ctx, WS_A_REF, alnref, (size_t)n_aln * 12, &dref))) return st;
+        if ((st = ctx->ensure(WS_A_AFFINE, (size_t)F * 12 * 8, &in.daff))) return st;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporaries above are read by then)
+        if ((st = mkamd_align_transforms_dev(ctx, (const float*)in.dxyz, M, F, (const float*)dref, n_aln, 1, (const uint32_t*)dsel,
+                                             (const uint32_t*)drefsel, n_aln, nullptr, F, 0, 0, (double*)in.daff, nullptr)))
+            return st;
+    } else {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return MKAMD_OK;
+}
+
+extern "C" int mkamd_group_moments_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* alnsel, const float* alnref,
+                                        int64_t n_aln, const uint32_t* atoms, const uint32_t* offsets, const float* weights, int64_t G, int mode,
+                                        float* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || G < 0 || n_aln < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (mode < mkamd::MOM_CENTER || mode > mkamd::MOM_SPHERICAL) return fail(MKAMD_EINVAL, "mode must be 0 (center), 1 (gyration) or 2 (spherical)");
+    if (F > 0x3fffffffLL || G > 0x3fffffffLL) return fail(MKAMD_EINVAL, "too many frames or groups (>= 2^30)");
+    if (F == 0 || G == 0) return MKAMD_OK;
+    if (!offsets || !out) return fail(MKAMD_EINVAL, "NULL pointer");
+    const int64_t n_sel = offsets[G];
+    MomHostInputs in;
+    if ((st = mom_host_inputs(ctx, coords, N, F, alnsel, alnref, n_aln, atoms, n_sel, offsets, G, weights, in))) return st;
+    const size_t bytes = (size_t)F * (mode == mkamd::MOM_SPHERICAL ? 3 : mode == mkamd::MOM_GYRATION ? 4 * (size_t)G : 3 * (size_t)G) * 4;
+    void* dout;
+    if ((st = ctx->ensure(WS_H_OUT, bytes, &dout, 0))) return st;
+    st = mkamd_group_moments_dev(ctx, (const float*)in.dxyz, in.rows, F, (const double*)in.daff, (const uint32_t*)in.datoms, (const uint32_t*)in.doffs,
+                                 (const float*)in.dw, G, n_sel, in.max_group, mode, (float*)dout);
+    if (st) return st;
+    return ctx->to_host(out, dout, bytes);
+} MK_API_CATCH
+
+extern "C" int mkamd_fluctuation_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* alnsel, const float* alnref,
+                                      int64_t n_aln, const uint32_t* atoms, int64_t n_sel, const uint32_t* offsets, int64_t G, const double* ref,
+                                      double* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || G < 0 || n_aln < 0 || n_sel < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (F > 0x3fffffffLL || G > 0x3fffffffLL || n_sel > 0x3fffffffLL) return fail(MKAMD_EINVAL, "too many frames, groups or atoms");
+    if (F == 0 || n_sel == 0 || (offsets && G == 0)) return MKAMD_OK;
+    if (!out) return fail(MKAMD_EINVAL, "NULL pointer");
+    MomHostInputs in;
+    if ((st = mom_host_inputs(ctx, coords, N, F, alnsel, alnref, n_aln, atoms, n_sel, offsets, G, nullptr, in))) return st;
+    void *dref = nullptr, *dout;
+    if (ref) {
+        if ((st = upload(ctx, WS_M_REFIN, ref, (size_t)n_sel * 24, &dref))) return st;
+    }
+    const size_t bytes = (size_t)F * (size_t)(offsets ? G : n_sel) * 8;
+    if ((st = ctx->ensure(WS_H_OUT, bytes, &dout, 0))) return st;
+    st = mkamd_fluctuation_dev(ctx, (const float*)in.dxyz, in.rows, F, (const double*)in.daff, (const uint32_t*)in.datoms, n_sel,
+                               (const uint32_t*)in.doffs, G, in.max_group, (const double*)dref, (double*)dout);
     if (st) return st;
     return ctx->to_host(out, dout, bytes);
 } MK_API_CATCH

@@ -44,6 +44,8 @@ enum WsSlot {
     WS_A_REFPART, WS_A_PART, WS_A_RPART, WS_A_FOLD, WS_A_REFFOLD, WS_A_SLAB, WS_A_XYZ, WS_A_REF, WS_A_SEL, WS_A_REFSEL, WS_A_FRAMES, WS_A_AFFINE,
     // surface area (sasa_pipeline.h) and its host entry point
     WS_S_POINTS, WS_S_PACK, WS_S_AREA, WS_S_ERR, WS_S_SLAB, WS_S_XYZ, WS_S_RADII, WS_S_MAP, WS_S_MASK, WS_S_OUT,
+    // group moments (moments_pipeline.h) and their host entry points
+    WS_M_PART, WS_M_REF, WS_M_ATOMS, WS_M_OFFS, WS_M_W, WS_M_REFIN,
     WS_NSLOTS
 };
 
