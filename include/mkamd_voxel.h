@@ -284,6 +284,36 @@ int mkamd_voxelize_lattice_topo_dev(mkamd_ctx* ctx, int32_t n_items, const float
                                     int64_t total_atoms, const mkamd_topology* topology, const double* d_origins,
                                     const int32_t* nvoxels, double voxelsize, const float* d_box, int32_t max_images_per_atom,
                                     const double* d_affine, float* d_features);
+/* A BATCH handle (round 7): the same contents for a RESIDENT, RAGGED BATCH OF DIFFERENT MOLECULES whose sigmas never change while
+ * its coordinates, origins and affines do (a shard a ShardedVoxelizer owns; augmentation epochs over one data set).  Built over the
+ * sigmas of ALL atoms of the batch, [total_atoms, n_channels], and indexed by an atom's position in the batch; `atom_offsets_host`
+ * ([n_items + 1], HOST memory in both forms, starting at 0 and ending at total_atoms; empty items are fine) is kept with it.
+ * More than 15 distinct sigma values in the whole batch: MKAMD_EINVAL, the caller keeps the plain call.
+ *   mkamd_voxelize_lattice_topo_dev       with a batch handle: the whole batch (n_items and total_atoms the handle's);
+ *   mkamd_voxelize_lattice_topo_range_dev its items [first_item, first_item + n_items): d_coords, d_atom_offsets (rebased: they
+ *       start at 0), d_origins, d_box, d_affine and d_features are the RANGE's.  (The range is named by its first ITEM: the first
+ *       atom follows from the handle's offsets, and an atom index cannot tell an empty item from its neighbour.)
+ * The call's items must be the handle's -- the same atoms of the batch, item by item: CHECKED on the device against the handle's
+ * offsets (a mismatch raises MKAMD_EINVAL at the next mkamd_ctx_synchronize / _poll_errors and indexes nothing of the handle's); the
+ * range itself (first_item + n_items within the handle, total_atoms the range's) is checked at once.  Features are the plain call's
+ * BIT FOR BIT; force_general and a value tolerance are refused as for a frame handle.  The handle is USED where the plain call takes
+ * the count / scan / fill chain in front of the tile kernels (any call of more than a few thousand atoms per item, every pipelined
+ * big call); a call the library routes elsewhere -- ligand-sized items, one small molecule, a direct binning pass -- is served as the
+ * plain call on the handle's own sigma copy, bit for bit as well.  mkamd_topology_batch_used answers which of the two a range would
+ * get under the context's current settings (`promised` != 0: the calls will come with mkamd_ctx_promise_inputs), so that a caller
+ * need not keep a handle that would never be used.  mkamd_topology_info's n_atoms is total_atoms for a batch handle;
+ * mkamd_topology_batch_info gives n_items (0: a frame handle) and the longest item. */
+int mkamd_topology_create_batch_dev(mkamd_ctx* ctx, const void* d_sigmas, int sigmas_are_f64, int64_t total_atoms, int32_t n_channels,
+                                    double voxelsize, const int64_t* atom_offsets_host, int32_t n_items, mkamd_topology** topology);
+int mkamd_topology_create_batch_host(mkamd_ctx* ctx, const void* sigmas, int sigmas_are_f64, int64_t total_atoms, int32_t n_channels,
+                                     double voxelsize, const int64_t* atom_offsets_host, int32_t n_items, mkamd_topology** topology);
+int mkamd_topology_batch_info(const mkamd_topology* topology, int32_t* n_items, int64_t* longest_item);
+int mkamd_topology_batch_used(mkamd_ctx* ctx, const mkamd_topology* topology, int32_t first_item, int32_t n_items, const int32_t* nvoxels,
+                              int32_t periodic, int32_t max_images_per_atom, int32_t promised, int32_t* used);
+int mkamd_voxelize_lattice_topo_range_dev(mkamd_ctx* ctx, int32_t n_items, const float* d_coords, const int64_t* d_atom_offsets,
+                                          int64_t total_atoms, const mkamd_topology* topology, int32_t first_item, const double* d_origins,
+                                          const int32_t* nvoxels, double voxelsize, const float* d_box, int32_t max_images_per_atom,
+                                          const double* d_affine, float* d_features);
 
 /* (4) lattice centres (voxeldescriptors.py:125-132 + :245-247), float64 [V,3], bit-exact with the
  * reference's numpy arithmetic: centre = fl64(index*voxelsize) + bb_min. */

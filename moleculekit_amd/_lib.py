@@ -81,6 +81,11 @@ SIGNATURES = {
     "mkamd_topology_destroy": (_c_int, [_vp, _vp]),
     "mkamd_topology_info": (_c_int, [_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i32), ctypes.POINTER(_c_dbl), ctypes.POINTER(_c_i32)]),
     "mkamd_voxelize_lattice_topo_dev": (_c_int, [_vp, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_dbl, _vp, _c_i32, _vp, _vp]),
+    "mkamd_topology_create_batch_dev": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i32, _c_dbl, _vp, _c_i32, ctypes.POINTER(_vp)]),
+    "mkamd_topology_create_batch_host": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i32, _c_dbl, _vp, _c_i32, ctypes.POINTER(_vp)]),
+    "mkamd_topology_batch_info": (_c_int, [_vp, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64)]),
+    "mkamd_topology_batch_used": (_c_int, [_vp, _vp, _c_i32, _c_i32, _vp, _c_i32, _c_i32, _c_i32, ctypes.POINTER(_c_i32)]),
+    "mkamd_voxelize_lattice_topo_range_dev": (_c_int, [_vp, _c_i32, _vp, _vp, _c_i64, _vp, _c_i32, _vp, _vp, _c_dbl, _vp, _c_i32, _vp, _vp]),
     "mkamd_grid_centers_host": (_c_int, [_vp, _vp, _vp, _c_dbl, _vp]),
     "mkamd_grid_centers_dev": (_c_int, [_vp, _vp, _vp, _c_dbl, _vp]),
     "mkamd_lattice_from_centers": (_c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp]),
@@ -443,8 +448,16 @@ class Context:
                                                      _ptr(d_out)))
 
     def voxelize_lattice_topo_dev(self, B, d_coords, d_offsets, total_atoms, topology, d_origins, nvox, voxelsize, d_box, max_images, d_out,
-                                  d_affine=None):
-        """``voxelize_lattice_dev`` for items that are each one set of coordinates of ``topology``'s molecule (include/mkamd_voxel.h)."""
+                                  d_affine=None, first_item=0):
+        """``voxelize_lattice_dev`` for items that are each one set of coordinates of ``topology``'s molecule, or -- a batch
+        topology -- its items [first_item, first_item + B) (include/mkamd_voxel.h)."""
+        if topology.n_items:
+            _check(load().mkamd_voxelize_lattice_topo_range_dev(self._h, B, _ptr(d_coords), _ptr(d_offsets), int(total_atoms), topology._h,
+                                                                int(first_item), _ptr(d_origins), _ptr(nvox), float(voxelsize), _ptr(d_box),
+                                                                int(max_images), _ptr(d_affine), _ptr(d_out)))
+            return
+        if first_item:
+            raise ValueError("first_item names a range of a BATCH topology's items")
         _check(load().mkamd_voxelize_lattice_topo_dev(self._h, B, _ptr(d_coords), _ptr(d_offsets), int(total_atoms), topology._h,
                                                       _ptr(d_origins), _ptr(nvox), float(voxelsize), _ptr(d_box), int(max_images),
                                                       _ptr(d_affine), _ptr(d_out)))
@@ -518,31 +531,54 @@ class Context:
 class Topology:
     """What the voxelizer's pre-pass derives from a molecule's sigmas ALONE, kept on the device for every later call over
     coordinates of that molecule (include/mkamd_voxel.h, (3c)): ``sigmas`` is the molecule's [n_atoms, C] matrix -- a numpy
-    array (float32 / float64) or a CUDA tensor of the context's device.  The library keeps its own copy."""
+    array (float32 / float64) or a CUDA tensor of the context's device.  The library keeps its own copy.
 
-    def __init__(self, ctx, sigmas, voxelsize):
+    The batch form -- ``atom_offsets`` given (host integers [n_items + 1], starting at 0) --: ``sigmas`` are those of ALL atoms of a
+    resident, ragged batch of different molecules, and a call voxelizes a contiguous range of its items
+    (``batch.voxelize_lattice_torch(topology=..., topology_first_item=...)``).  ``n_items`` is 0 for the one-molecule form."""
+
+    def __init__(self, ctx, sigmas, voxelsize, atom_offsets=None):
         self._h = _vp(None)
         self._ctx = ctx
+        self.n_items = 0
         h = _vp(None)
+        offs = None
+        if atom_offsets is not None:
+            offs = np.ascontiguousarray(atom_offsets, dtype=np.int64).reshape(-1)
+            if offs.size < 2:
+                raise ValueError("a batch topology needs at least one item")
+        batch_args = () if offs is None else (_ptr(offs), int(offs.size - 1))
         if isinstance(sigmas, np.ndarray) or not hasattr(sigmas, "data_ptr"):
             sig = np.ascontiguousarray(sigmas)
             if sig.dtype not in (np.float32, np.float64):
                 sig = sig.astype(np.float64)
             if sig.ndim != 2:
                 raise ValueError("sigmas must be (natoms, nchannels)")
-            _check(load().mkamd_topology_create_host(ctx._h, _ptr(sig), int(sig.dtype == np.float64), int(sig.shape[0]), int(sig.shape[1]),
-                                                     float(voxelsize), ctypes.byref(h)))
+            create = load().mkamd_topology_create_host if offs is None else load().mkamd_topology_create_batch_host
+            _check(create(ctx._h, _ptr(sig), int(sig.dtype == np.float64), int(sig.shape[0]), int(sig.shape[1]),
+                          float(voxelsize), *batch_args, ctypes.byref(h)))
             self.n_atoms, self.n_channels = int(sig.shape[0]), int(sig.shape[1])
         else:
             import torch
             if not (sigmas.is_cuda and sigmas.dim() == 2 and sigmas.is_contiguous() and sigmas.dtype in (torch.float32, torch.float64)):
                 raise ValueError("sigmas must be a contiguous float32 / float64 CUDA tensor (natoms, nchannels)")
             ctx.set_stream(torch.cuda.current_stream(sigmas.device).cuda_stream)
-            _check(load().mkamd_topology_create_dev(ctx._h, int(sigmas.data_ptr()), int(sigmas.dtype == torch.float64), int(sigmas.shape[0]),
-                                                    int(sigmas.shape[1]), float(voxelsize), ctypes.byref(h)))
+            create = load().mkamd_topology_create_dev if offs is None else load().mkamd_topology_create_batch_dev
+            _check(create(ctx._h, int(sigmas.data_ptr()), int(sigmas.dtype == torch.float64), int(sigmas.shape[0]),
+                          int(sigmas.shape[1]), float(voxelsize), *batch_args, ctypes.byref(h)))
             self.n_atoms, self.n_channels = int(sigmas.shape[0]), int(sigmas.shape[1])
         self._h = h
         self.voxelsize = float(voxelsize)
+        self.n_items = 0 if offs is None else int(offs.size - 1)
+
+    def used_for(self, first_item, n_items, nvoxels, periodic=False, max_images=1, promised=False) -> bool:
+        """A batch topology: would a call on its items [first_item, first_item + n_items) use it (the count / scan / fill chain), or
+        be served as a plain call on the library's sigma copy?  Decided by the library, with the context's current settings."""
+        nv = np.ascontiguousarray(nvoxels, dtype=np.int32).reshape(3)
+        u = _c_i32(0)
+        _check(load().mkamd_topology_batch_used(self._ctx._h, self._h, int(first_item), int(n_items), _ptr(nv), int(bool(periodic)),
+                                                int(max_images), int(bool(promised)), ctypes.byref(u)))
+        return bool(u.value)
 
     @property
     def has_wide_sigmas(self) -> bool:

@@ -185,12 +185,13 @@ def rotation_affines(rotations, centers):
 
 
 def voxelize_lattice_torch(coords, atom_offsets, sigmas, origins, nvoxels, voxelsize, box=None,
-                           max_images=1, out=None, ctx=None, channel_first=False, affine=None, topology=None):
+                           max_images=1, out=None, ctx=None, channel_first=False, affine=None, topology=None, topology_first_item=0):
     """Same as ``voxelize_lattice`` on torch CUDA tensors; asynchronous on torch's current stream.
 
     ``topology`` (``_lib.Topology``, with ``sigmas=None``): every item is one set of coordinates of that molecule -- the frames
     of a trajectory; what the pre-pass derives from the sigmas is taken from the handle (include/mkamd_voxel.h (3c)): the same
-    features bit for bit, fewer instructions per call.
+    features bit for bit, fewer instructions per call.  A BATCH topology (``_lib.Topology(..., atom_offsets=...)``): the items are
+    its items [``topology_first_item``, + B) -- the same atoms, new coordinates / origins / affines; ``atom_offsets`` start at 0.
 
     coords float32 [sumN,3], atom_offsets int64 [B+1], sigmas float32|float64 [sumN,C],
     origins float64 [B,3], box float32 [B,3] or None (pass ``max_images`` from
@@ -238,7 +239,7 @@ def voxelize_lattice_torch(coords, atom_offsets, sigmas, origins, nvoxels, voxel
         ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
         if topology is not None:
             ctx.voxelize_lattice_topo_dev(B, coords.data_ptr(), atom_offsets.data_ptr(), int(coords.shape[0]), topology, origins.data_ptr(), nv,
-                                          float(voxelsize), d_box, int(max_images), out.data_ptr(), d_aff)
+                                          float(voxelsize), d_box, int(max_images), out.data_ptr(), d_aff, first_item=int(topology_first_item))
         else:
             ctx.voxelize_lattice_dev(B, coords.data_ptr(), atom_offsets.data_ptr(), int(coords.shape[0]),
                                      sigmas.data_ptr(), sigmas.dtype == torch.float64, C, origins.data_ptr(), nv,

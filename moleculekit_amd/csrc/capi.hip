@@ -300,8 +300,10 @@ struct mkamd_ctx {
 // A molecule's topology on the device (include/mkamd_voxel.h, mkamd_topology_create_*): one allocation, owned here.
 struct mkamd_topology {
     int device = 0;
-    void* mem = nullptr;                   // sigmas copy | cw | ids | table | flags
+    void* mem = nullptr;                   // sigmas copy | cw | ids | table | flags | wide list | atom offsets (a batch handle)
     mkamd::TopologyDev dev;
+    std::vector<long long> h_offsets;      // a batch handle: its atom offsets and its wide list on the host (dev.h_offsets, dev.h_wide_list)
+    std::vector<unsigned> h_wide;
 };
 
 // `pending_ok`: the entry point may run between the two halves of a host call (mkamd_voxelize_lattice_host_begin / _end): the
@@ -328,7 +330,7 @@ static int collect_async_errors(mkamd_ctx* ctx)
     HIP_TRY(hipMemcpy(&flag, ctx->bufs[WS_ERR], sizeof(int), hipMemcpyDeviceToHost));
     if (flag == 0) return 0;
     HIP_TRY(hipMemset(ctx->bufs[WS_ERR], 0, sizeof(int)));
-    if (flag & MK_ERR_TOPOLOGY) return fail(MKAMD_EINVAL, "a topology call was given an item that is not the topology's atom count long; results are incomplete");
+    if (flag & MK_ERR_TOPOLOGY) return fail(MKAMD_EINVAL, "a topology call was given an item that is not the topology's atom count long (a batch topology: not the atoms of its item); results are incomplete");
     if (flag & MK_ERR_BAD_BOX) return fail(MKAMD_EBOX, "periodic box edges must be > 10 A (2 x cutoff)");
     if (flag & MK_ERR_TOO_MANY_IMAGES) return fail(MKAMD_EBOX, "periodic box much smaller than the grid (too many images)");
     return fail(MKAMD_EOVERFLOW, "more periodic images than max_images_per_atom allowed; results are incomplete");
@@ -881,7 +883,8 @@ static int voxelize_lattice_dev_impl(mkamd_ctx* ctx, int32_t B, const float* d_c
                                      const int64_t* d_atom_offsets, int64_t total_atoms, const void* d_sigmas,
                                      int sigmas_are_f64, int32_t C, const double* d_origins,
                                      const int32_t* nvoxels, double voxelsize, const float* d_box,
-                                     int32_t max_images, const double* d_affine, float* d_features, const mkamd_topology* topo)
+                                     int32_t max_images, const double* d_affine, float* d_features, const mkamd_topology* topo,
+                                     int32_t topo_first_item = 0)
 {
     int st = check_ctx(ctx);
     if (st) return st;
@@ -898,6 +901,7 @@ static int voxelize_lattice_dev_impl(mkamd_ctx* ctx, int32_t B, const float* d_c
     P.coords = d_coords; P.atom_offsets = (const long long*)d_atom_offsets; P.sigmas = d_sigmas;
     P.origins = d_origins; P.box = d_box; P.affine = d_affine; P.out = d_features;
     P.topo = topo ? &topo->dev : nullptr;
+    P.topo_first_item = topo_first_item;
     std::string err;
     // a promise (mkamd_ctx_promise_inputs) is about the next call of THIS entry point made from outside the library: a host
     // call reaches here through voxelize_lattice_host_begin_impl, which has set the promise aside (its inputs were uploaded
@@ -919,20 +923,31 @@ try {
 } MK_API_CATCH
 
 // ---- topology reuse: the frames of a trajectory share everything the pre-pass derives from the sigmas ----
-int mkamd_topology_create_dev(mkamd_ctx* ctx, const void* d_sigmas, int sigmas_are_f64, int64_t n_atoms, int32_t C, double voxelsize,
-                              mkamd_topology** out)
-try {
+// h_offsets != nullptr: a BATCH handle over the n_items items of those (host) atom offsets, n_atoms = all their atoms
+static int topology_create_impl(mkamd_ctx* ctx, const void* d_sigmas, int sigmas_are_f64, int64_t n_atoms, int32_t C, double voxelsize,
+                                const int64_t* h_offsets, int32_t n_items, mkamd_topology** out)
+{
     if (!out) return fail(MKAMD_EINVAL, "topology out-pointer is NULL");
     *out = nullptr;
     int st = check_ctx(ctx);
     if (st) return st;
     if (n_atoms <= 0 || C <= 0 || !d_sigmas) return fail(MKAMD_EINVAL, "a topology needs n_atoms > 0, n_channels > 0 and the sigmas");
     if (n_atoms > 0x7fffffffLL) return fail(MKAMD_EINVAL, "a topology holds at most 2^31 atoms");
+    long long max_item = 0;
+    if (h_offsets) {
+        if (n_items <= 0 || h_offsets[0] != 0 || h_offsets[n_items] != n_atoms)
+            return fail(MKAMD_EINVAL, "a batch topology needs n_items > 0 and atom offsets that start at 0 and end at total_atoms");
+        for (int32_t b = 0; b < n_items; ++b) {
+            if (h_offsets[b + 1] < h_offsets[b]) return fail(MKAMD_EINVAL, "a batch topology's atom offsets must not decrease");
+            max_item = std::max<long long>(max_item, h_offsets[b + 1] - h_offsets[b]);
+        }
+    }
     const int G = ceil_div(C, CHG);
     const size_t a256 = 255, sig_bytes = (size_t)n_atoms * C * (sigmas_are_f64 ? 8 : 4);
     const size_t o_cw = (sig_bytes + a256) & ~a256, o_ids = (o_cw + (size_t)n_atoms * G * sizeof(uint2) + a256) & ~a256,
                  o_tab = (o_ids + (size_t)n_atoms * G * sizeof(unsigned) + a256) & ~a256, o_flags = o_tab + 256, o_wide = o_flags + 256,
-                 total = o_wide + (size_t)n_atoms * sizeof(unsigned);
+                 o_offs = (o_wide + (size_t)n_atoms * sizeof(unsigned) + a256) & ~a256,
+                 total = o_offs + (h_offsets ? (size_t)n_items + 1 : 0) * sizeof(long long);
     mkamd_topology* t = new mkamd_topology();
     t->device = ctx->device;
     hipError_t e = hipMalloc(&t->mem, total);
@@ -952,9 +967,10 @@ try {
         (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return drop(hip_fail(e, "topology read-back"));
     const int flags = flags2[0];
     const unsigned n_wide = (unsigned)flags2[1];
-    if (n_wide > 1u) {
+    std::vector<unsigned>& wl = t->h_wide;                           // (a batch handle keeps the list on the host too)
+    wl.resize(n_wide);
+    if (n_wide > 1u || (n_wide != 0u && h_offsets)) {
         // the list arrives in the order the lanes' atomics did: sorted here, once, so that a handle is the same whenever it is built
-        std::vector<unsigned> wl(n_wide);
         if ((e = hipMemcpyAsync(wl.data(), m + o_wide, (size_t)n_wide * 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
             (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return drop(hip_fail(e, "topology read-back (wide atoms)"));
         std::sort(wl.begin(), wl.end());
@@ -967,8 +983,44 @@ try {
     t->dev.sigmas = m; t->dev.cw = (const uint2*)(m + o_cw); t->dev.ids = (const unsigned*)(m + o_ids); t->dev.table = (const unsigned*)(m + o_tab);
     t->dev.overflow = false; t->dev.wide = (flags & 1) != 0;
     t->dev.wide_list = (const unsigned*)(m + o_wide); t->dev.n_wide = n_wide;
+    if (h_offsets) {
+        t->h_offsets.assign(h_offsets, h_offsets + n_items + 1);
+        if ((e = hipMemcpyAsync(m + o_offs, t->h_offsets.data(), ((size_t)n_items + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return drop(hip_fail(e, "topology upload (atom offsets)"));
+        t->dev.batch = true; t->dev.n_items = n_items; t->dev.max_item = max_item;
+        t->dev.offsets = (const long long*)(m + o_offs); t->dev.h_offsets = t->h_offsets.data(); t->dev.h_wide_list = t->h_wide.data();
+    }
     *out = t;
     return MKAMD_OK;
+}
+
+int mkamd_topology_create_dev(mkamd_ctx* ctx, const void* d_sigmas, int sigmas_are_f64, int64_t n_atoms, int32_t C, double voxelsize,
+                              mkamd_topology** out)
+try {
+    return topology_create_impl(ctx, d_sigmas, sigmas_are_f64, n_atoms, C, voxelsize, nullptr, 0, out);
+} MK_API_CATCH
+
+// ---- a batch handle: the same for a resident, ragged batch of different molecules (include/mkamd_voxel.h (3c)) ----
+int mkamd_topology_create_batch_dev(mkamd_ctx* ctx, const void* d_sigmas, int sigmas_are_f64, int64_t total_atoms, int32_t C, double voxelsize,
+                                    const int64_t* atom_offsets_host, int32_t n_items, mkamd_topology** out)
+try {
+    if (!atom_offsets_host) { if (out) *out = nullptr; return fail(MKAMD_EINVAL, "a batch topology needs the batch's atom offsets (host memory)"); }
+    return topology_create_impl(ctx, d_sigmas, sigmas_are_f64, total_atoms, C, voxelsize, atom_offsets_host, n_items, out);
+} MK_API_CATCH
+
+int mkamd_topology_create_batch_host(mkamd_ctx* ctx, const void* sigmas, int sigmas_are_f64, int64_t total_atoms, int32_t C, double voxelsize,
+                                     const int64_t* atom_offsets_host, int32_t n_items, mkamd_topology** out)
+try {
+    if (!out) return fail(MKAMD_EINVAL, "topology out-pointer is NULL");
+    *out = nullptr;
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (total_atoms <= 0 || C <= 0 || !sigmas) return fail(MKAMD_EINVAL, "a topology needs n_atoms > 0, n_channels > 0 and the sigmas");
+    void* ds = nullptr;
+    const size_t bytes = (size_t)total_atoms * C * (sigmas_are_f64 ? 8 : 4);
+    if ((st = ctx->ensure(WS_H_SIGMAS, bytes, &ds))) return st;
+    HIP_TRY(hipMemcpyAsync(ds, sigmas, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return mkamd_topology_create_batch_dev(ctx, ds, sigmas_are_f64, total_atoms, C, voxelsize, atom_offsets_host, n_items, out);
 } MK_API_CATCH
 
 int mkamd_topology_create_host(mkamd_ctx* ctx, const void* sigmas, int sigmas_are_f64, int64_t n_atoms, int32_t C, double voxelsize,
@@ -1019,6 +1071,53 @@ try {
     if (!topo) return fail(MKAMD_EINVAL, "topology is NULL");
     return voxelize_lattice_dev_impl(ctx, B, d_coords, d_atom_offsets, total_atoms, nullptr, topo->dev.sigmas_f64, topo->dev.C, d_origins, nvoxels,
                                      voxelsize, d_box, max_images, d_affine, d_features, topo);
+} MK_API_CATCH
+
+int mkamd_voxelize_lattice_topo_range_dev(mkamd_ctx* ctx, int32_t B, const float* d_coords, const int64_t* d_atom_offsets, int64_t total_atoms,
+                                          const mkamd_topology* topo, int32_t first_item, const double* d_origins, const int32_t* nvoxels,
+                                          double voxelsize, const float* d_box, int32_t max_images, const double* d_affine, float* d_features)
+try {
+    if (!topo) return fail(MKAMD_EINVAL, "topology is NULL");
+    if (!topo->dev.batch) return fail(MKAMD_EINVAL, "a range of items is a call on a batch topology (mkamd_topology_create_batch_*)");
+    return voxelize_lattice_dev_impl(ctx, B, d_coords, d_atom_offsets, total_atoms, nullptr, topo->dev.sigmas_f64, topo->dev.C, d_origins, nvoxels,
+                                     voxelsize, d_box, max_images, d_affine, d_features, topo, first_item);
+} MK_API_CATCH
+
+int mkamd_topology_batch_info(const mkamd_topology* topo, int32_t* n_items, int64_t* longest_item)
+try {
+    if (!topo) return fail(MKAMD_EINVAL, "topology is NULL");
+    if (n_items) *n_items = topo->dev.batch ? topo->dev.n_items : 0;
+    if (longest_item) *longest_item = topo->dev.batch ? (int64_t)topo->dev.max_item : 0;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+// Would a call on items [first_item, + n_items) of a batch handle use it -- take the count / scan / fill chain in front of the tile
+// kernels -- or be served as a plain call on the handle's sigma copy?  The path is chosen where every call's is (choose_lattice_path,
+// settle_lattice_path), with the context's settings as they are now; `promised`: the call will come with mkamd_ctx_promise_inputs.
+int mkamd_topology_batch_used(mkamd_ctx* ctx, const mkamd_topology* topo, int32_t first_item, int32_t n_items, const int32_t* nvoxels,
+                              int32_t periodic, int32_t max_images, int32_t promised, int32_t* used)
+try {
+    if (!ctx || !topo || !nvoxels || !used) return fail(MKAMD_EINVAL, "ctx / topology / nvoxels / used is NULL");
+    *used = 0;
+    const TopologyDev& t = topo->dev;
+    if (!t.batch) return fail(MKAMD_EINVAL, "not a batch topology");
+    if (first_item < 0 || n_items < 0 || (long long)first_item + n_items > (long long)t.n_items) return fail(MKAMD_EINVAL, "not a range of the batch topology's items");
+    LatticeProblem P;
+    P.B = n_items; P.total_atoms = t.h_offsets[first_item + n_items] - t.h_offsets[first_item]; P.C = t.C; P.sigmas_f64 = t.sigmas_f64;
+    P.nvox[0] = nvoxels[0]; P.nvox[1] = nvoxels[1]; P.nvox[2] = nvoxels[2];
+    P.voxelsize = t.voxelsize; P.pbc = periodic ? 1 : 0; P.max_images = periodic ? max_images : 1;
+    P.tile_k = ctx->tile_k; P.force_general = ctx->force_general; P.lds_tier = ctx->lds_tier; P.prepass_mode = ctx->prepass_mode; P.tile_team = ctx->tile_team; P.tile_items = ctx->tile_items; P.exact_redo_list = ctx->exact_redo; P.fine_cells = ctx->fine_cells; P.value_tol = ctx->value_tol; P.direct = ctx->direct;
+    P.topo = &t; P.topo_first_item = first_item;
+    GridDesc g;
+    std::string err;
+    int st = plan_lattice(P, g, err);
+    if (st) return fail(st, err);
+    if (P.B == 0 || g.V == 0 || P.total_atoms == 0 || g.force_general || g.reach_tau > 0.f) return MKAMD_OK;
+    const bool may_pipeline = (ctx->pipelining || promised) && ctx->side_stream && !ctx->pipeline_broken;
+    LatticePath L = choose_lattice_path(P, g, may_pipeline);
+    settle_lattice_path(L, P, g, may_pipeline && L.pipelined_wanted);
+    *used = L.topo() ? 1 : 0;
+    return MKAMD_OK;
 } MK_API_CATCH
 
 // End of a small synchronous call (tens of microseconds of GPU work): poll the stream instead of blocking on it -- the

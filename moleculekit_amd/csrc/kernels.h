@@ -111,7 +111,20 @@ struct GridDesc {
     // were built once from its sigmas: sigma-side arrays are indexed by the atom's index INSIDE its item
     long long topo_n;
     unsigned topo_wide;         // atoms of that molecule with a sigma wide enough for the exact cut-off fix-up (the handle lists them)
+    // a BATCH handle (round 7): built over all atoms of a resident, ragged batch of DIFFERENT molecules; the call is a contiguous
+    // range of its items.  topo_offsets != nullptr says so (wave-uniform): the handle's atom offsets, standing at the call's first
+    // item, whose first atom is the handle's atom topo_base.  The host hands every sigma-side array over AT that atom (ids, channel
+    // words, the sigma copy), so they are indexed by the atom's index in the CALL -- never folded into one molecule -- and an item is
+    // the handle's when both its ends are: topo_offsets[b] == topo_base + atom_offsets[b], the same for b + 1.  topo_n is then the
+    // longest item of the handle (k_exact_redo's slices) and topo_wide the wide atoms inside the range (the fix-up's jobs).
+    const long long* topo_offsets;
+    long long topo_base;
 };
+// is item b of a batch-handle call (GridDesc::topo_offsets) the handle's item -- the same atoms of the resident batch?
+MK_DEV bool topo_batch_item_ok(const GridDesc& g, const long long* __restrict__ atom_offsets, int b)
+{
+    return g.topo_offsets[b] == g.topo_base + atom_offsets[b] && g.topo_offsets[b + 1] == g.topo_base + atom_offsets[b + 1];
+}
 enum { DIRECT_FAILED = 0, DIRECT_SPILLED = 1, DIRECT_WORDS = 4, DIRECT_HEAD = 32 /* words in front of the counters (one 128-byte line) */ };
 constexpr float REACH_STEP = 0.17f;   // levels 0..3: reach 5.00 / 4.56 / 4.06 / 3.50 A at the 5 A cutoff (H at eps = 1e-6: 3.48 A)
 
@@ -437,10 +450,13 @@ MK_DEV void bin_atom(const GridDesc& g, long long a, bool act, int b_lo, int b_h
             }
             b = lo;
             const long long first = atom_offsets[b];
-            if (atom_offsets[b + 1] - first != g.topo_n) {
-                mk_atomic_or(err_flag, MK_ERR_TOPOLOGY);         // not a frame of the molecule the topology was built from
+            // a frame of the handle's molecule: its ids stand at the atom's index inside the item; an item of a batch handle: at the
+            // atom's index in the call (GridDesc::topo_offsets)
+            const bool batch = g.topo_offsets != nullptr;
+            if (batch ? !topo_batch_item_ok(g, atom_offsets, b) : atom_offsets[b + 1] - first != g.topo_n) {
+                mk_atomic_or(err_flag, MK_ERR_TOPOLOGY);         // not a frame of the molecule / not the items the topology was built from
             } else {
-                const unsigned* __restrict__ ids = reinterpret_cast<const unsigned*>(sigmas) + (size_t)(a - first) * g.G;
+                const unsigned* __restrict__ ids = reinterpret_cast<const unsigned*>(sigmas) + (size_t)(batch ? a : a - first) * g.G;
                 unsigned* __restrict__ park_ids = reinterpret_cast<unsigned*>(tmp_cls) + (size_t)a * g.G;
                 for (int gq = 0; gq < g.G; ++gq) {
                     const unsigned v = ids[gq];
@@ -2751,7 +2767,8 @@ MK_DEV void exact_recompute(const GridDesc& g, int b, int ix, int iy, int iz, un
     if (g.pbc) { L[0] = (double)box[3 * (size_t)b]; L[1] = (double)box[3 * (size_t)b + 1]; L[2] = (double)box[3 * (size_t)b + 2]; }
     const long long a_lo = atom_offsets[b], a_end = atom_offsets[b + 1];
     const long long a_hi = a_end - a_lo > s_hi ? a_lo + s_hi : a_end;     // (the end of this wave's slice)
-    const long long sshift = g.topo_n ? a_lo : 0;                         // topology calls: the molecule's one sigma matrix
+    // a frame of a topology call: the molecule's one sigma matrix; an item of a batch handle: its own rows, at the atom's index in the call
+    const long long sshift = (g.topo_n && g.topo_offsets == nullptr) ? a_lo : 0;
     const float fcx = (float)cx, fcy = (float)cy, fcz = (float)cz;
     const float fL[3] = {(float)L[0], (float)L[1], (float)L[2]};
     const float fiL[3] = {1.0f / fL[0], 1.0f / fL[1], 1.0f / fL[2]};
@@ -2970,6 +2987,18 @@ MK_DEV void exact_fixup_block(const GridDesc& g, const unsigned blk, int per_ite
     const int lane = threadIdx.x;
     const float wmax = g.w_exact_max;
     auto wide_bits = [&](unsigned bits) { return bits != CLS_EMPTY && mk_uint_as_float(bits) < wmax; };   // NaN: false
+    if (per_item == 2 && g.topo_offsets != nullptr) {
+        // a batch handle: `summary` = the handle's wide atoms inside the call's range (batch-wide indices, ascending), a job each;
+        // the atom's item follows from the call's offsets.  An item that is not the handle's (the binning has raised
+        // MK_ERR_TOPOLOGY) indexes nothing of the handle's.
+        const long long a = (long long)summary[blk] - g.topo_base;
+        if (a < 0 || a >= total_atoms) return;
+        const int b = item_of_atom(atom_offsets, g.B, a, 0);
+        if (!topo_batch_item_ok(g, atom_offsets, b)) return;
+        exact_fixup_atom<SigT, LIST_ONLY>(g, b, a, a, coords, atom_offsets, sigmas, origins, box, affine, out, s_best, s_near, feedback, seq,
+                                          redo_list, redo_cap);
+        return;
+    }
     if (per_item == 2) {
         const int b = (int)(blk / g.topo_wide);
         const long long k = (long long)summary[blk % g.topo_wide];         // the atom's index inside the molecule
@@ -3129,6 +3158,8 @@ MK_KERNEL(64) void k_exact_redo(GridDesc g, unsigned* __restrict__ redo_list, un
     for (unsigned long long job = blockIdx.x; job < jobs; job += gridDim.x) {          // block-uniform
         const unsigned* e = redo_list + REDO_HEAD + (size_t)(job / slices) * REDO_ENTRY;
         const long long s_lo = (long long)(job % slices) * REDO_SLICE;
+        // (a batch handle: topo_n is its LONGEST item -- this item may end before the slice starts)
+        if (g.topo_offsets != nullptr && s_lo >= atom_offsets[e[0] + 1] - atom_offsets[e[0]]) continue;
         const unsigned long long chs = (unsigned long long)e[4] | ((unsigned long long)e[5] << 32);
         exact_recompute<SigT>(g, (int)e[0], (int)e[1], (int)e[2], (int)e[3], chs, (int)e[6], coords, atom_offsets, sigmas, origins, box, affine, out,
                               s_best, s_near, s_lo, s_lo + REDO_SLICE, true);

@@ -66,6 +66,15 @@ struct TopologyDev {
     bool wide = false;                      // some sigma is wide enough for the exact cut-off fix-up (GridDesc::w_exact_max)
     const unsigned* wide_list = nullptr;    // [n_wide] the atoms that have one, ascending (k_tail's fix-up jobs of a topology call: item x wide atom)
     unsigned n_wide = 0;
+    // A BATCH handle (round 7): the same contents built over ALL atoms of a resident, ragged batch of different molecules -- n atoms
+    // in n_items items -- and indexed by an atom's position in that batch.  A call is a contiguous range of its items
+    // (LatticeProblem::topo_first_item); wide_list then holds batch-wide atom indices.
+    bool batch = false;
+    int n_items = 0;
+    const long long* offsets = nullptr;     // [n_items + 1] the atom offsets the handle was built for, on the device (the binning checks the call's against them)
+    const long long* h_offsets = nullptr;   // the same on the host (a call's range: its first atom, its atom count)
+    const unsigned* h_wide_list = nullptr;  // wide_list on the host (the wide atoms inside a call's range)
+    long long max_item = 0;                 // atoms of the longest item (k_exact_redo's slices)
 };
 
 struct LatticeProblem {
@@ -100,6 +109,7 @@ struct LatticeProblem {
     const double* affine = nullptr;        // optional [B,12]: rotation (row-major 3x3) + translation per item
     float* out = nullptr;
     const TopologyDev* topo = nullptr;      // every item is topo->n atoms of that molecule (checked on the device: MK_ERR_TOPOLOGY)
+    int topo_first_item = 0;                // a batch handle: the call is its items [topo_first_item, + B) (checked on the device too)
 };
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
@@ -277,10 +287,23 @@ struct LatticePath {
     bool per_item() const { return prepass == PRE_ITEMS; }
 };
 
+// The exact cut-off fix-up of the path's pre-pass: its jobs, the waves that share them, and whether they run split in three launches.
+inline void choose_exact_fixup(LatticePath& L, const LatticeProblem& P, const GridDesc& g)
+{
+    const bool topo = L.topo();
+    const unsigned topo_jobs = !topo ? 0u : P.topo->batch ? g.topo_wide : (unsigned)((long long)g.B * P.topo->n_wide);
+    L.fix_jobs = topo ? topo_jobs : L.per_item() ? (unsigned)g.B : P.total_atoms > 0 ? (unsigned)ceil_div(P.total_atoms, 256) : 0u;
+    L.fix_waves = L.fix_jobs < 8192u ? L.fix_jobs : 8192u;         // (the fix-up waves share the jobs: see k_tail)
+    // a trajectory of a molecule with wide sigmas (ions): the exact recomputes of k_tail's hits are spread over many waves (k_exact_redo)
+    L.split_exact_fixup = topo && topo_jobs != 0u && P.seq == 0u && !g.force_general && P.exact_redo_list >= 0;
+}
+
 inline LatticePath choose_lattice_path(const LatticeProblem& P, const GridDesc& g, bool pipelining_possible)
 {
     LatticePath L;
-    const bool topo = P.topo != nullptr;
+    // a frame handle takes the chain whatever the call's size; a BATCH handle is honoured where the plain call would take the chain
+    // (and no direct pass: settle_lattice_path) -- a call that goes elsewhere is a plain call on the handle's own sigma copy
+    const bool topo = P.topo != nullptr && !P.topo->batch, topo_batch = P.topo != nullptr && P.topo->batch;
     const long long B = g.B;
     // Big batches are software-pipelined across calls: the pre-pass (latency / atomic bound) of this call
     // runs on an internal stream beside the tile kernel (VALU bound) of the previous call, on the other
@@ -321,7 +344,8 @@ inline LatticePath choose_lattice_path(const LatticeProblem& P, const GridDesc& 
     const bool per_item = !topo && !solo && hist_fits && P.prepass_mode != 0 &&
                           (P.prepass_mode == 1 || (P.total_atoms <= 4096LL * B && !chain_pays));
     // a topology call (P.topo): the chain with the TOPO binning kernels
-    L.prepass = topo ? LatticePath::PRE_CHAIN_TOPO : solo ? LatticePath::PRE_SOLO : per_item ? LatticePath::PRE_ITEMS : LatticePath::PRE_CHAIN;
+    L.prepass = topo ? LatticePath::PRE_CHAIN_TOPO : solo ? LatticePath::PRE_SOLO : per_item ? LatticePath::PRE_ITEMS
+              : topo_batch ? LatticePath::PRE_CHAIN_TOPO : LatticePath::PRE_CHAIN;
     L.pipelined_wanted = big && !per_item && !solo;
     // spill slots PER ITEM (k_bin_solo: every atom of the call, so that it cannot run out)
     L.spill = solo ? (unsigned)P.total_atoms : P.spill_cap > 0 ? P.spill_cap : (unsigned)std::max<long long>(1024, P.total_atoms / (8LL * B));
@@ -329,12 +353,10 @@ inline LatticePath choose_lattice_path(const LatticeProblem& P, const GridDesc& 
     // the exact cut-off fix-up: jobs per 256-atom block, per item, or per (item, WIDE atom of the molecule) -- the handle lists
     // them -- or none at all.  (Round 5: one job per item; a wave then walked all of a 30 000-atom frame 64 atoms at a time and
     // took its wide atoms one after the other.)
-    L.fix_jobs = topo ? (unsigned)(B * P.topo->n_wide) : per_item ? (unsigned)g.B : P.total_atoms > 0 ? (unsigned)ceil_div(P.total_atoms, 256) : 0u;
-    L.fix_waves = L.fix_jobs < 8192u ? L.fix_jobs : 8192u;         // (the fix-up waves share the jobs: see k_tail)
+    // (a batch handle: per wide atom inside the call's range, GridDesc::topo_wide)
+    choose_exact_fixup(L, P, g);
     // (the general path has no dense tiles; its fix-up waves still run, and its statistics stay what they were)
     L.dense_wgs = g.force_general ? 0u : (unsigned)(tile_waves < 4096ull ? tile_waves : 4096ull);
-    // a trajectory of a molecule with wide sigmas (ions): the exact recomputes of k_tail's hits are spread over many waves (k_exact_redo)
-    L.split_exact_fixup = topo && P.topo->n_wide != 0u && P.seq == 0u && !g.force_general && P.exact_redo_list >= 0;
     L.redo_cap = P.exact_redo_list > 0 && (unsigned)P.exact_redo_list < REDO_CAP ? (unsigned)P.exact_redo_list : REDO_CAP;   // (a tiny list: tests of the overflow pass)
     return L;
 }
@@ -352,10 +374,13 @@ inline void settle_lattice_path(LatticePath& L, const LatticeProblem& P, GridDes
     // k_bin_direct for a big call: whenever asked for (1), and by itself (-1) when the call is NOT pipelined -- in order
     // the one-pass form is 3 % faster (the class table of the previous call on the workspace serves; the chain behind
     // it leaves at once), beside the previous call's tile kernel it gains nothing
-    const bool direct_big = L.prepass == LatticePath::PRE_CHAIN && L.direct_geom &&
+    // (a BATCH handle's call that would take the direct pass IS a plain call: the pass reads sigma rows, the handle's own copy serves)
+    const bool chain_or_batch = L.prepass == LatticePath::PRE_CHAIN || (L.topo() && P.topo->batch);
+    const bool direct_big = chain_or_batch && L.direct_geom &&
                             (P.direct == 1 || (P.direct < 0 && !set_is_pipelined && P.total_atoms >= PIPELINE_MIN_ATOMS));
     L.direct_layout = (L.solo() || direct_big) && L.direct_slots <= 0xFFFF0000ull;
     L.direct_first = L.direct_layout && !L.solo();
+    if (L.direct_first && L.topo()) { L.prepass = LatticePath::PRE_CHAIN; choose_exact_fixup(L, P, g); }
     // a small call (one grid): one launch instead of three dependent ones
     L.small_scan = !L.direct_layout && (size_t)g.B * (size_t)g.cstride <= SMALL_PREPASS_MAX_CELLS &&
                    (unsigned)ceil_div(P.total_atoms > 0 ? P.total_atoms : 1, 256) <= SMALL_PREPASS_MAX_BLOCKS;
@@ -619,12 +644,14 @@ int launch_tiles(BE& be, int tier, const LatticeProblem& P, const LatticePath& L
 
 // The lattice hot path: bin -> scan -> fill -> tile kernel.  All pointers in P are device pointers.
 template <class BE>
-int run_lattice(BE& be, const LatticeProblem& P, std::string& err)
+int run_lattice(BE& be, const LatticeProblem& P_in, std::string& err)
 {
+    LatticeProblem P = P_in;                // (a batch handle's call that leaves the chain becomes a plain call: see below)
     GridDesc g;
     int st = plan_lattice(P, g, err);
     if (st) return st;
     if (P.B == 0 || g.V == 0) return ST_OK;
+    size_t topo_wide_lo = 0;                // a batch handle: where the range's wide atoms start in its list
     // a topology call: what its binning kernels do not cover -- the general path, the tolerance-aware reach (it needs every
     // atom's smallest w at fill time) -- is refused, not approximated
     if (const TopologyDev* t = P.topo) {
@@ -632,17 +659,46 @@ int run_lattice(BE& be, const LatticeProblem& P, std::string& err)
             err = "a topology call takes the class-sorted path only: not with more than 15 distinct sigmas, force_general or a value tolerance (use the plain entry point)";
             return ST_EINVAL;
         }
-        if (t->C != P.C || t->voxelsize != P.voxelsize || t->n <= 0 || P.total_atoms != (long long)P.B * t->n) {
+        if (t->C != P.C || t->voxelsize != P.voxelsize || t->n <= 0 || (!t->batch && P.total_atoms != (long long)P.B * t->n)) {
             err = "the topology was built for another channel count / voxel size, or the call is not n_items x its atom count long";
             return ST_EINVAL;
         }
-        if ((unsigned long long)g.B * t->n_wide > 0xffffffffull) { err = "too many (item, wide atom) fix-up jobs (>= 2^32): split the batch"; return ST_EINVAL; }
-        g.topo_n = t->n; g.topo_wide = t->n_wide;
+        if (t->batch) {
+            const long long i0 = P.topo_first_item;
+            if (i0 < 0 || i0 + P.B > (long long)t->n_items || P.total_atoms != t->h_offsets[i0 + P.B] - t->h_offsets[i0]) {
+                err = "the call is not a range of the batch topology's items: first item + n_items beyond its items, or another atom count";
+                return ST_EINVAL;
+            }
+            // the range's first atom, the handle's offsets from its first item on, the wide atoms inside it (the list is ascending)
+            g.topo_base = t->h_offsets[i0]; g.topo_offsets = t->offsets + i0; g.topo_n = t->max_item;
+            const unsigned* w0 = std::lower_bound(t->h_wide_list, t->h_wide_list + t->n_wide, (unsigned)g.topo_base);
+            const unsigned* w1 = std::lower_bound(w0, t->h_wide_list + t->n_wide, (unsigned)(g.topo_base + P.total_atoms));
+            topo_wide_lo = (size_t)(w0 - t->h_wide_list); g.topo_wide = (unsigned)(w1 - w0);
+        } else {
+            if ((unsigned long long)g.B * t->n_wide > 0xffffffffull) { err = "too many (item, wide atom) fix-up jobs (>= 2^32): split the batch"; return ST_EINVAL; }
+            g.topo_n = t->n; g.topo_wide = t->n_wide;
+        }
     }
     LatticePath L = choose_lattice_path(P, g, be.pipelining_possible());
     g.cls_per_item = L.per_item() ? 1 : 0;
     const int set = be.acquire_set(L.pipelined_wanted);
     settle_lattice_path(L, P, g, be.set_is_pipelined(set));
+    TopologyDev range;                      // a batch handle as the call's range sees it: every sigma-side array at the range's first atom
+    if (P.topo != nullptr && P.topo->batch) {
+        const TopologyDev* t = P.topo;
+        const size_t a0 = (size_t)g.topo_base;
+        const void* sig0 = (const char*)t->sigmas + a0 * (size_t)t->C * (t->sigmas_f64 ? 8 : 4);
+        if (L.topo()) {
+            range = *t;
+            range.ids = t->ids + a0 * (size_t)t->G; range.cw = t->cw + a0 * (size_t)t->G; range.sigmas = sig0;
+            range.wide_list = t->wide_list + topo_wide_lo;
+            P.topo = &range;
+        } else {
+            // not the chain (ligand-sized items, one small call, a direct pass): a plain call on the handle's own copy of the sigmas
+            P.topo = nullptr; P.sigmas = sig0; P.sigmas_f64 = t->sigmas_f64;
+            g.topo_n = 0; g.topo_wide = 0u; g.topo_offsets = nullptr; g.topo_base = 0;
+        }
+    }
     if (L.solo() && !L.direct_layout) { err = "internal: the one-launch pre-pass does not fit its record slots"; return ST_EINVAL; }
 
     LatticeWorkspace W;

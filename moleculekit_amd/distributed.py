@@ -206,6 +206,40 @@ class ShardedVoxelizer:
             if self._topo is None:
                 self._d["sigmas"] = self._d["sigmas"].repeat(self.n_local, 1).contiguous()
                 self._shared = False
+        elif (compute is None and self.n_local > 0 and int(self._offs_host[-1]) > 0 and os.environ.get("MKAMD_BATCH_TOPOLOGY", "1") != "0"
+              and not self._items_repeat_one_molecule(sig)):
+            # A batch of DIFFERENT molecules: the shard is resident and its sigmas are never written again (see above), so what the
+            # pre-pass derives from them -- per atom of the shard -- is built once as well (a BATCH topology handle, include/mkamd_voxel.h
+            # (3c)); coordinates, origins and affines may change from call to call, the sigmas do not.  Kept only where the library says
+            # the shard's calls would use it (ligand-sized items and one-molecule calls take other pre-passes), never for the A-B modes
+            # of a context; more than 15 distinct sigmas: the plain call.  MKAMD_BATCH_TOPOLOGY=0 (read here, once): the plain call.
+            # self._d["sigmas"] stays resident either way (other callers slice it).
+            # Items that all repeat ONE sigma matrix are frames of one molecule: `shared_sigmas` is the handle for those (one copy of the
+            # matrix), and a caller who leaves it off there asks for the plain call -- the cross-check of the frame handle, the
+            # benchmark's plain leg of its trajectory workloads -- and gets it.
+            from . import _lib
+            tctx = self._ctx or _lib.default_context(self.device.index if self.device.index is not None else 0)
+            if not getattr(tctx, "_force_general", False) and not getattr(tctx, "_value_tol", 0.0):
+                torch.cuda.current_stream(self.device).synchronize()
+                try:
+                    topo = _lib.Topology(tctx, self._d["sigmas"], self.voxelsize, atom_offsets=self._offs_host)
+                    if topo.used_for(0, self.n_local, self.nvoxels, periodic=self._d["box"] is not None, max_images=self.max_images,
+                                     promised=self.pipelined):
+                        self._topo = topo
+                    else:
+                        topo.close()
+                except ValueError:                                         # more than 15 distinct sigmas
+                    self._topo = None
+
+    def _items_repeat_one_molecule(self, sig):
+        """Do all items (more than one) carry the same sigma rows -- frames of one molecule?  Host side, at construction; the
+        comparison stops at the first item that differs (a batch of different molecules: at once)."""
+        sizes = np.diff(self._offs_host)
+        n0 = int(sizes[0])
+        if self.n_local < 2 or n0 <= 0 or not np.all(sizes == n0) or sig.ndim != 2 or sig.shape[0] != n0 * self.n_local:
+            return False
+        rows = sig.reshape(self.n_local, n0, -1)
+        return all(np.array_equal(rows[0], r) for r in rows[1:])
 
     # ---- construction -------------------------------------------------------------------------------------
     @classmethod
@@ -260,7 +294,7 @@ class ShardedVoxelizer:
         return out
 
     # ---- compute ------------------------------------------------------------------------------------------
-    def _run(self, coords, offs, sigmas, origins, box, out=None):
+    def _run(self, coords, offs, sigmas, origins, box, first_item=0, out=None):
         if self._compute is not None:
             t = lambda x: None if x is None else x.numpy()
             res = self._compute(t(coords), t(offs), t(sigmas), t(origins), self.nvoxels, self.voxelsize, t(box))
@@ -274,7 +308,8 @@ class ShardedVoxelizer:
         if self.pipelined:
             ctx.promise_inputs(None)          # resident since _upload's host-side wait: complete, and nobody writes them
         return batch.voxelize_lattice_torch(coords, offs, None if self._topo is not None else sigmas, origins, self.nvoxels, self.voxelsize,
-                                            box=box, max_images=self.max_images, out=out, ctx=ctx, topology=self._topo)
+                                            box=box, max_images=self.max_images, out=out, ctx=ctx, topology=self._topo,
+                                            topology_first_item=first_item if self._topo is not None and self._topo.n_items else 0)
 
     def _items(self, lo, hi):
         """Views of the resident shard for local items [lo, hi) (the rebased offsets are built once per range)."""
@@ -290,7 +325,7 @@ class ShardedVoxelizer:
                 offs = torch.as_tensor(self._offs_host[lo:hi + 1] - a0, device=self.device)
                 self._chunk_offs[(lo, hi)] = offs
         sig = d["sigmas"] if self._shared else d["sigmas"][a0:a1]       # (shared: the molecule's one matrix, the topology stands in for it)
-        return d["coords"][a0:a1], offs, sig, d["origins"][lo:hi], None if d["box"] is None else d["box"][lo:hi]
+        return d["coords"][a0:a1], offs, sig, d["origins"][lo:hi], None if d["box"] is None else d["box"][lo:hi], lo
 
     def voxelize(self, out=None):
         """This rank's shard -> float32 [B_local, V, C] on its device; asynchronous, no collective."""
