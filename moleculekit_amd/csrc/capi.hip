@@ -20,6 +20,8 @@
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -36,6 +38,13 @@ static int fail(int code, const char* msg) noexcept
     return code;
 }
 static int fail(int code, const std::string& msg) noexcept { return fail(code, msg.c_str()); }
+
+// what an entry point returns after a run_* of the pipelines: its status, with the message it left (if any) as the last error
+static int run_status(int st, const std::string& err) noexcept
+{
+    if (st) return err.empty() ? st : fail(st, err);
+    return MKAMD_OK;
+}
 
 static int hip_fail(hipError_t e, const char* what) noexcept
 {
@@ -771,8 +780,7 @@ try {
     std::string err;
     st = run_centers(*ctx, d_centers, n_centers, d_coords, n_atoms, d_sigmas, sigmas_are_f64, n_channels,
                      box_host, d_features, err);
-    if (st && !err.empty()) return fail(st, err);
-    return st;
+    return run_status(st, err);
 } MK_API_CATCH
 
 int mkamd_occupancy_centers_host(mkamd_ctx* ctx, const double* centers, int64_t V, const float* coords,
@@ -908,8 +916,7 @@ static int voxelize_lattice_dev_impl(mkamd_ctx* ctx, int32_t B, const float* d_c
     // on the main stream just now, behind the marker a pipelined pre-pass waits for)
     st = run_lattice(*ctx, P, err);
     ctx->promise = false; ctx->promise_event = nullptr;       // one call's worth
-    if (st && !err.empty()) return fail(st, err);
-    return st;
+    return run_status(st, err);
 }
 
 int mkamd_voxelize_lattice_aug_dev(mkamd_ctx* ctx, int32_t B, const float* d_coords,
@@ -959,7 +966,7 @@ static int topology_create_impl(mkamd_ctx* ctx, const void* d_sigmas, int sigmas
     std::string err;
     st = run_topology_build(*ctx, m, sigmas_are_f64, (long long)n_atoms, C, voxelsize, (uint2*)(m + o_cw), (unsigned*)(m + o_ids),
                             (unsigned*)(m + o_tab), (int*)(m + o_flags), (unsigned*)(m + o_wide), err);
-    if (st) return drop(err.empty() ? st : fail(st, err));
+    if (st) return drop(run_status(st, err));
     unsigned table[CLS_TABLE_WORDS];
     int flags2[2] = {0, 0};
     if ((e = hipMemcpyAsync(table, m + o_tab, sizeof table, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
@@ -1430,8 +1437,7 @@ try {
     const int nv[3] = {nvoxels[0], nvoxels[1], nvoxels[2]};
     std::string err;
     st = run_grid_centers(*ctx, bb_min, nv, voxelsize, d_centers, err);
-    if (st && !err.empty()) return fail(st, err);
-    return st;
+    return run_status(st, err);
 } MK_API_CATCH
 
 int mkamd_grid_centers_host(mkamd_ctx* ctx, const double* bb_min, const int32_t* nvoxels, double voxelsize,
@@ -1505,8 +1511,10 @@ try {
     return mkamd::lattice_from_centers(c, (long long)V, bb_min, nvoxels, voxelsize) ? 1 : 0;
 } catch (...) { return 0; }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------
-// distance_utils row (include/mkamd_distance.h)
+// what the _host entry points of the trajectory metrics share: validate, stage (pack, upload), run, download
 // ---------------------------------------------------------------------------------------------
 static int upload(mkamd_ctx* ctx, int slot, const void* src, size_t bytes, void** dst)
 try {
@@ -1515,6 +1523,81 @@ try {
     if (bytes) HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return 0;
 } MK_API_CATCH
+
+// every index of a list below N, or "<what> index out of range"
+template <class T>
+static int check_indices(const T* idx, int64_t n, int64_t N, const char* what)
+{
+    for (int64_t i = 0; i < n; ++i)
+        if ((uint64_t)(int64_t)idx[i] >= (uint64_t)N) {              // (a negative index of a signed list is out of range as well)
+            char msg[96];
+            snprintf(msg, sizeof msg, "%s index out of range", what);
+            return fail(MKAMD_EINVAL, msg);
+        }
+    return 0;
+}
+
+// The coordinates ([N][3][F]) of a host call and what names their atoms, on the way up.  Only the rows of the atoms the call's index
+// lists name go up (host_pack.h), with the lists and the per-atom arrays in the packed numbering, when those atoms are few and avoid
+// bit 32 is clear -- or whatever their number (`always`: group moments); the caller's arrays as they are otherwise.
+struct HostStage {
+    using List = std::pair<const uint32_t*, int64_t>;                // atom indices and their number
+    mkamd_ctx* ctx;
+    const float* coords;
+    int64_t N, F;
+    mkamd::PackedAtoms pk;
+    std::vector<std::shared_ptr<const void>> held;                   // the rewritten arrays, until sync()
+
+    HostStage(mkamd_ctx* ctx_, const float* coords_, int64_t N_, int64_t F_, std::initializer_list<List> lists, bool always = false)
+        : ctx(ctx_), coords(coords_), N(N_), F(F_)
+    {
+        for (const List& l : lists) if (l.first) pk.collect(l.first, l.second);
+        if (always || !(ctx->dist_avoid & 32)) pk.finish(coords, N, F, ctx->packed_coords, always);
+    }
+    int64_t rows() const { return pk.on ? pk.size() : N; }           // atoms of the array that goes up
+    const float* host_rows() const { return pk.on ? ctx->packed_coords.data() : coords; }
+    int coords_to(int slot, void** d) { return upload(ctx, slot, host_rows(), (size_t)rows() * 3 * F * 4, d); }
+    template <class T>
+    const T* hold(std::vector<T> v)
+    {
+        auto p = std::make_shared<const std::vector<T>>(std::move(v));
+        held.push_back(p);
+        return p->data();
+    }
+    template <class T>                                               // an index list: in the numbering of the rows that went up
+    int list_to(int slot, const T* idx, int64_t n, void** d) { return upload(ctx, slot, pk.on ? hold(pk.remap(idx, n)) : idx, (size_t)n * sizeof(T), d); }
+    template <class T>                                               // one value per atom (chain ids, masses): those of the rows that went up
+    int per_atom_to(int slot, const T* values, void** d) { return upload(ctx, slot, pk.on ? hold(pk.gather(values)) : values, (size_t)rows() * sizeof(T), d); }
+    int sync()                                                       // the copies have read `held` and the packed rows (the caller's arrays need no wait)
+    {
+        if (pk.on) HIP_TRY(hipStreamSynchronize(ctx->stream));
+        held.clear();
+        return 0;
+    }
+    void unpack_in_place(std::vector<uint32_t>& atoms) const { if (pk.on) pk.unpack_in_place(atoms.data(), atoms.size()); }   // results that name atoms
+};
+
+// [rows][F] of the host -> frame-major [F][rows] on the device: up into `slab_slot`, transposed into `xyz_slot`
+static int upload_frame_major(mkamd_ctx* ctx, int slab_slot, int xyz_slot, const float* src, int64_t rows, int64_t F, void** d_xyz)
+{
+    int st;
+    void* dslab;
+    if ((st = upload(ctx, slab_slot, src, (size_t)rows * F * 4, &dslab))) return st;
+    if ((st = ctx->ensure(xyz_slot, (size_t)rows * F * 4, d_xyz))) return st;
+    return mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dslab, rows, F, F, 1.0f, (float*)*d_xyz);
+}
+
+// a result down to the caller's array; `prefault`: a big one's pages are touched first (prefault_big_result)
+static int download(mkamd_ctx* ctx, void* dst, const void* d_src, size_t bytes, bool prefault)
+{
+    if (prefault) prefault_big_result(dst, bytes);
+    return ctx->to_host(dst, d_src, bytes);
+}
+
+// ---------------------------------------------------------------------------------------------
+// distance_utils row (include/mkamd_distance.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" {
 
 int64_t mkamd_dist_count_pairs(int64_t n1, int64_t n2, int selfdist) { return count_pairs(n1, n2, selfdist); }
 
@@ -1526,8 +1609,7 @@ try {
     if (st) return st;
     std::string err;
     st = run_dist_trajectory(*ctx, d_coords, F, d_box, d_sel1, n1, d_sel2, n2, d_chains, selfdist, pbc, squared, d_results, err, ctx->dist_avoid);
-    if (st && !err.empty()) return fail(st, err);
-    return st;
+    return run_status(st, err);
 } MK_API_CATCH
 
 int mkamd_dist_trajectory_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const float* box,
@@ -1540,34 +1622,20 @@ try {
     const int64_t P = count_pairs(n1, n2, selfdist);
     if (F == 0 || P == 0) return MKAMD_OK;
     if (!coords || !box || !sel1 || !sel2 || !chains || !results) return fail(MKAMD_EINVAL, "NULL pointer");
-    for (int64_t i = 0; i < n1; ++i) if (sel1[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel1 index out of range");
-    for (int64_t i = 0; i < n2; ++i) if (sel2[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel2 index out of range");
+    if ((st = check_indices(sel1, n1, N, "sel1")) || (st = check_indices(sel2, n2, N, "sel2"))) return st;
     void *dc, *db, *d1, *d2, *dch, *dout;
-    // only the selected atoms' rows go up when they are few (host_pack.h); the selections and chain ids in the packed numbering
-    mkamd::PackedAtoms pk;
-    pk.collect(sel1, n1); pk.collect(sel2, n2);
-    if (!(ctx->dist_avoid & 32) && pk.finish(coords, N, F, ctx->packed_coords)) {
-        const std::vector<uint32_t> p1 = pk.remap(sel1, n1), p2 = pk.remap(sel2, n2), pc = pk.gather(chains);
-        if ((st = upload(ctx, WS_H_COORDS, ctx->packed_coords.data(), (size_t)pk.size() * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, p1.data(), (size_t)n1 * 4, &d1))) return st;
-        if ((st = upload(ctx, WS_D_SEL2, p2.data(), (size_t)n2 * 4, &d2))) return st;
-        if ((st = upload(ctx, WS_D_CHAINS, pc.data(), (size_t)pk.size() * 4, &dch))) return st;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporaries above are read by then)
-    } else {
-        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)N * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, sel1, (size_t)n1 * 4, &d1))) return st;
-        if ((st = upload(ctx, WS_D_SEL2, sel2, (size_t)n2 * 4, &d2))) return st;
-        if ((st = upload(ctx, WS_D_CHAINS, chains, (size_t)N * 4, &dch))) return st;
-    }
+    HostStage up(ctx, coords, N, F, {{sel1, n1}, {sel2, n2}});
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.list_to(WS_D_SEL1, sel1, n1, &d1))) return st;
+    if ((st = up.list_to(WS_D_SEL2, sel2, n2, &d2))) return st;
+    if ((st = up.per_atom_to(WS_D_CHAINS, chains, &dch))) return st;
+    if ((st = up.sync())) return st;
     if ((st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
     if ((st = ctx->ensure(WS_H_OUT, (size_t)F * P * 4, &dout, 0))) return st;
     st = mkamd_dist_trajectory_dev(ctx, (const float*)dc, F, (const float*)db, (const uint32_t*)d1, n1, (const uint32_t*)d2, n2,
                                    (const uint32_t*)dch, selfdist, pbc, squared, (float*)dout);
     if (st) return st;
-    prefault_big_result(results, (size_t)F * P * 4);
-    HIP_TRY(hipMemcpyAsync(results, dout, (size_t)F * P * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return MKAMD_OK;
+    return download(ctx, results, dout, (size_t)F * P * 4, true);
 } MK_API_CATCH
 
 // contacts_trajectory / get_collisions on the device (dist_kernels.h: count -> scan -> fill per chunk of frames)
@@ -1586,33 +1654,23 @@ try {
     const int64_t P = count_pairs(n1, n2, selfdist);
     if (F == 0 || P == 0) return MKAMD_OK;
     if (!coords || !box || !sel1 || !sel2 || !chains) return fail(MKAMD_EINVAL, "NULL pointer");
-    for (int64_t i = 0; i < n1; ++i) if (sel1[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel1 index out of range");
-    for (int64_t i = 0; i < n2; ++i) if (sel2[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel2 index out of range");
+    if ((st = check_indices(sel1, n1, N, "sel1")) || (st = check_indices(sel2, n2, N, "sel2"))) return st;
     void *dc, *db, *d1, *d2, *dch;
-    mkamd::PackedAtoms pk;                                           // (host_pack.h: only the selected atoms' rows go up when they are few)
-    pk.collect(sel1, n1); pk.collect(sel2, n2);
-    if (!(ctx->dist_avoid & 32) && pk.finish(coords, N, F, ctx->packed_coords)) {
-        const std::vector<uint32_t> p1 = pk.remap(sel1, n1), p2 = pk.remap(sel2, n2), pc = pk.gather(chains);
-        if ((st = upload(ctx, WS_H_COORDS, ctx->packed_coords.data(), (size_t)pk.size() * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, p1.data(), (size_t)n1 * 4, &d1))) return st;
-        if ((st = upload(ctx, WS_D_SEL2, p2.data(), (size_t)n2 * 4, &d2))) return st;
-        if ((st = upload(ctx, WS_D_CHAINS, pc.data(), (size_t)pk.size() * 4, &dch))) return st;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    } else {
-        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)N * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, sel1, (size_t)n1 * 4, &d1))) return st;
-        if ((st = upload(ctx, WS_D_SEL2, sel2, (size_t)n2 * 4, &d2))) return st;
-        if ((st = upload(ctx, WS_D_CHAINS, chains, (size_t)N * 4, &dch))) return st;
-    }
+    HostStage up(ctx, coords, N, F, {{sel1, n1}, {sel2, n2}});
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.list_to(WS_D_SEL1, sel1, n1, &d1))) return st;
+    if ((st = up.list_to(WS_D_SEL2, sel2, n2, &d2))) return st;
+    if ((st = up.per_atom_to(WS_D_CHAINS, chains, &dch))) return st;
+    if ((st = up.sync())) return st;
     if ((st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
     std::string err;
     static_assert(sizeof(long long) == sizeof(int64_t), "frame offsets are int64");
     st = run_contacts(*ctx, (const float*)dc, (long long)F, (const float*)db, (const unsigned*)d1, (long long)n1, (const unsigned*)d2,
                       (long long)n2, (const unsigned*)dch, selfdist, pbc, dist_threshold, (size_t)256 << 20,
                       (long long*)frame_offsets, HostPairSink<mkamd_ctx>{*ctx, ctx->contacts_host}, err);
-    if (st) return err.empty() ? st : fail(st, err);
+    if (st) return run_status(st, err);
     if (ctx->contacts_host.empty()) return MKAMD_OK;
-    if (pk.on) pk.unpack_in_place(ctx->contacts_host.data(), ctx->contacts_host.size());     // the list names atoms of the caller's array
+    up.unpack_in_place(ctx->contacts_host);                          // the list names atoms of the caller's array
     *pairs = ctx->contacts_host.data();
     return MKAMD_OK;
 } MK_API_CATCH
@@ -1633,30 +1691,14 @@ try {
     if ((reduction1 == 1 || reduction2 == 1) && !masses) return fail(MKAMD_EINVAL, "masses are required for the com reduction");
     for (int64_t g = 0; g < ng1; ++g) if (g1_off[g + 1] <= g1_off[g]) return fail(MKAMD_EINVAL, "empty group in groups1");
     for (int64_t g = 0; g < ng2; ++g) if (g2_off[g + 1] <= g2_off[g]) return fail(MKAMD_EINVAL, "empty group in groups2");
-    for (int64_t k = 0; k < g1_off[ng1]; ++k) if (g1_atoms[k] < 0 || g1_atoms[k] >= N) return fail(MKAMD_EINVAL, "groups1 atom index out of range");
-    for (int64_t k = 0; k < g2_off[ng2]; ++k) if (g2_atoms[k] < 0 || g2_atoms[k] >= N) return fail(MKAMD_EINVAL, "groups2 atom index out of range");
+    if ((st = check_indices(g1_atoms, g1_off[ng1], N, "groups1 atom")) || (st = check_indices(g2_atoms, g2_off[ng2], N, "groups2 atom"))) return st;
     void *dc, *db, *a1, *o1, *a2, *o2, *c1, *c2, *dm = nullptr, *dout;
-    int64_t n_up = N;                                                // atoms of the array that goes up
-    mkamd::PackedAtoms pk;                                           // (host_pack.h: only the groups' atoms when they are few)
-    pk.collect(g1_atoms, g1_off[ng1]); pk.collect(g2_atoms, g2_off[ng2]);
-    if (!(ctx->dist_avoid & 32) && pk.finish(coords, N, F, ctx->packed_coords)) {
-        const std::vector<int32_t> p1 = pk.remap(g1_atoms, g1_off[ng1]), p2 = pk.remap(g2_atoms, g2_off[ng2]);
-        n_up = pk.size();
-        if ((st = upload(ctx, WS_H_COORDS, ctx->packed_coords.data(), (size_t)n_up * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_G1A, p1.data(), (size_t)g1_off[ng1] * 4, &a1))) return st;
-        if ((st = upload(ctx, WS_D_G2A, p2.data(), (size_t)g2_off[ng2] * 4, &a2))) return st;
-        if (masses) {
-            const std::vector<float> pm = pk.gather(masses);
-            if ((st = upload(ctx, WS_D_MASS, pm.data(), (size_t)n_up * 4, &dm))) return st;
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporaries above are read by then)
-    } else {
-        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)N * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_G1A, g1_atoms, (size_t)g1_off[ng1] * 4, &a1))) return st;
-        if ((st = upload(ctx, WS_D_G2A, g2_atoms, (size_t)g2_off[ng2] * 4, &a2))) return st;
-        if (masses && (st = upload(ctx, WS_D_MASS, masses, (size_t)N * 4, &dm))) return st;
-    }
+    HostStage up(ctx, coords, N, F, {{reinterpret_cast<const uint32_t*>(g1_atoms), g1_off[ng1]}, {reinterpret_cast<const uint32_t*>(g2_atoms), g2_off[ng2]}});
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.list_to(WS_D_G1A, g1_atoms, g1_off[ng1], &a1))) return st;
+    if ((st = up.list_to(WS_D_G2A, g2_atoms, g2_off[ng2], &a2))) return st;
+    if (masses && (st = up.per_atom_to(WS_D_MASS, masses, &dm))) return st;
+    if ((st = up.sync())) return st;
     if ((st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
     if ((st = upload(ctx, WS_D_G1O, g1_off, (size_t)(ng1 + 1) * 8, &o1))) return st;
     if ((st = upload(ctx, WS_D_G2O, g2_off, (size_t)(ng2 + 1) * 8, &o2))) return st;
@@ -1664,16 +1706,13 @@ try {
     if ((st = upload(ctx, WS_D_CHAINS2, chains2, (size_t)ng2 * 4, &c2))) return st;
     if ((st = ctx->ensure(WS_H_OUT, (size_t)F * P * 4, &dout, 0))) return st;
     std::string err;
-    st = run_dist_reduction(*ctx, (const float*)dc, n_up, F, (const float*)db, (const int*)a1, (const long long*)o1, ng1, g1_off[ng1], (const int*)a2,
+    st = run_dist_reduction(*ctx, (const float*)dc, up.rows(), F, (const float*)db, (const int*)a1, (const long long*)o1, ng1, g1_off[ng1], (const int*)a2,
                             (const long long*)o2, ng2, (const unsigned*)c1, (const unsigned*)c2, selfdist, pairs, pbc,
                             (const float*)dm, reduction1, reduction2, (float*)dout, err,
                             ctx->reduction_block ? ctx->reduction_block : reduction_block_for((const long long*)g1_off, ng1),
                             ctx->reduction_block == -2 ? 1 : ctx->reduction_block ? -1 : 0);
-    if (st) return err.empty() ? st : fail(st, err);
-    prefault_big_result(results, (size_t)F * P * 4);
-    HIP_TRY(hipMemcpyAsync(results, dout, (size_t)F * P * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return MKAMD_OK;
+    if (st) return run_status(st, err);
+    return download(ctx, results, dout, (size_t)F * P * 4, true);
 } MK_API_CATCH
 
 // ---- device-resident forms (round 6): coordinates, selections / groups and results stay on the GPU; asynchronous on the
@@ -1694,7 +1733,7 @@ try {
     DevicePairSink<mkamd_ctx> sink{*ctx};
     st = run_contacts(*ctx, d_coords, (long long)F, d_box, d_sel1, (long long)n1, d_sel2, (long long)n2, d_chains, selfdist, pbc,
                       dist_threshold, (size_t)256 << 20, (long long*)frame_offsets, sink, err);
-    if (st) return err.empty() ? st : fail(st, err);
+    if (st) return run_status(st, err);
     if (sink.size) *d_pairs = static_cast<const uint32_t*>(sink.base);
     return MKAMD_OK;
 } MK_API_CATCH
@@ -1720,8 +1759,7 @@ try {
                             (const int*)d_g2_atoms, (const long long*)d_g2_off, ng2, d_chains1, d_chains2, selfdist, pairs, pbc, d_masses,
                             reduction1, reduction2, d_results, err, ctx->reduction_block,
                             ctx->reduction_block == -2 ? 1 : ctx->reduction_block ? -1 : 0);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 int mkamd_cdist_dev(mkamd_ctx* ctx, const float* d_c1, int64_t n1, const float* d_c2, int64_t n2, int32_t D, float* d_results)
@@ -1733,8 +1771,7 @@ try {
     if (!d_c1 || !d_c2 || !d_results) return fail(MKAMD_EINVAL, "NULL pointer");
     std::string err;
     st = run_cdist(*ctx, d_c1, n1, d_c2, n2, D, d_results, err);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 int mkamd_pdist_dev(mkamd_ctx* ctx, const float* d_c, int64_t n, int32_t D, float* d_results)
@@ -1746,8 +1783,7 @@ try {
     if (!d_c || !d_results) return fail(MKAMD_EINVAL, "NULL pointer");
     std::string err;
     st = run_pdist(*ctx, d_c, n, D, d_results, err);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 int mkamd_cdist_host(mkamd_ctx* ctx, const float* c1, int64_t n1, const float* c2, int64_t n2, int32_t D, float* results)
@@ -1763,11 +1799,8 @@ try {
     if ((st = ctx->ensure(WS_H_OUT, (size_t)n1 * n2 * 4, &dout, 0))) return st;
     std::string err;
     st = run_cdist(*ctx, (const float*)d1, n1, (const float*)d2, n2, D, (float*)dout, err);
-    if (st) return err.empty() ? st : fail(st, err);
-    prefault_big_result(results, (size_t)n1 * n2 * 4);
-    HIP_TRY(hipMemcpyAsync(results, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return MKAMD_OK;
+    if (st) return run_status(st, err);
+    return download(ctx, results, dout, (size_t)n1 * n2 * 4, true);
 } MK_API_CATCH
 
 int mkamd_pdist_host(mkamd_ctx* ctx, const float* c, int64_t n, int32_t D, float* results)
@@ -1782,11 +1815,8 @@ try {
     if ((st = ctx->ensure(WS_H_OUT, (size_t)n * (n - 1) / 2 * 4, &dout, 0))) return st;
     std::string err;
     st = run_pdist(*ctx, (const float*)d1, n, D, (float*)dout, err);
-    if (st) return err.empty() ? st : fail(st, err);
-    prefault_big_result(results, (size_t)n * (n - 1) / 2 * 4);
-    HIP_TRY(hipMemcpyAsync(results, dout, (size_t)n * (n - 1) / 2 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return MKAMD_OK;
+    if (st) return run_status(st, err);
+    return download(ctx, results, dout, (size_t)n * (n - 1) / 2 * 4, true);
 } MK_API_CATCH
 
 }  // extern "C"
@@ -2029,8 +2059,7 @@ try {
     std::string err;
     st = mkamd::run_align_transforms(*ctx, align_args(d_xyz, N, F, d_ref, Nr, Fr, d_sel, d_refsel, n, d_frames, K, refframe, matching),
                                      d_affine, d_fit_rmsd, err);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 extern "C" int mkamd_align_apply_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, const int64_t* d_frames, int64_t K,
@@ -2042,8 +2071,7 @@ try {
     if ((((uintptr_t)d_xyz) | ((uintptr_t)d_out)) & 3) return fail(MKAMD_EINVAL, "coordinates must be 4-byte aligned");
     std::string err;
     st = mkamd::run_align_apply(*ctx, d_xyz, N, reinterpret_cast<const long long*>(d_frames), K, d_affine, d_out, err);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 extern "C" int mkamd_align_rmsd_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const float* d_ref, int64_t Nr, int64_t Fr,
@@ -2056,8 +2084,7 @@ try {
     std::string err;
     st = mkamd::run_align_rmsd(*ctx, align_args(d_xyz, N, F, d_ref, Nr, Fr, d_sel, d_refsel, n, d_frames, K, refframe, matching),
                                d_affine, d_rmsd, err);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 extern "C" int mkamd_align_host(mkamd_ctx* ctx, float* coords, int64_t N, int64_t F, const float* refcoords, int64_t Nr, int64_t Fr,
@@ -2071,8 +2098,7 @@ try {
     if (!coords || !refcoords || !frames || (n > 0 && (!sel || !refsel))) return fail(MKAMD_EINVAL, "NULL pointer");
     if (matching && Fr != F) return fail(MKAMD_EINVAL, "matchingframes needs a reference with as many frames as the trajectory");
     if (!matching && (refframe < 0 || refframe >= Fr)) return fail(MKAMD_EINVAL, "refframe out of range");
-    for (int64_t k = 0; k < n; ++k)
-        if ((int64_t)sel[k] >= N || (int64_t)refsel[k] >= Nr) return fail(MKAMD_EINVAL, "selection index out of range");
+    if ((st = check_indices(sel, n, N, "selection")) || (st = check_indices(refsel, n, Nr, "selection"))) return st;
     int64_t fmin = F, fmax = -1;
     for (int64_t i = 0; i < K; ++i) {
         if (frames[i] < 0 || frames[i] >= F) return fail(MKAMD_EINVAL, "frame index out of range");
@@ -2112,7 +2138,7 @@ try {
                                                       (const uint32_t*)drefsel, n, (const int64_t*)dframes, K, rf, matching),
                                      (double*)daff, nullptr, err);
     if (!st) st = mkamd::run_align_apply(*ctx, (const float*)dxyz, N, (const long long*)dframes, K, (const double*)daff, (float*)dxyz, err);
-    if (st) return err.empty() ? st : fail(st, err);
+    if (st) return run_status(st, err);
     // back to [3N][span], to the host, and only the listed frames into coords
     if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dxyz, span, rows, rows, 1.0f, (float*)dslab))) return st;
     std::vector<float> out((size_t)rows * span);
@@ -2147,8 +2173,7 @@ try {
     if (N > 0 && F > 0 && (!d_xyz || !d_radii || !d_mapping || !d_mask || !d_out)) return fail(MKAMD_EINVAL, "NULL pointer");
     std::string err;
     st = mkamd::run_sasa(*ctx, sasa_args(d_xyz, N, F, d_radii, n_points, d_mapping, d_mask, coord_div, d_out, n_out), err);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 extern "C" int mkamd_sasa_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* keep, int64_t n_keep,
@@ -2161,22 +2186,12 @@ try {
     const int64_t n = keep ? n_keep : N;
     if (n == 0 || F == 0) return MKAMD_OK;
     if (!coords || !radii || !mapping || !mask || !out) return fail(MKAMD_EINVAL, "NULL pointer");
-    for (int64_t k = 0; keep && k < n; ++k)
-        if ((int64_t)keep[k] >= N) return fail(MKAMD_EINVAL, "kept atom index out of range");
+    if (keep && (st = check_indices(keep, n, N, "kept atom"))) return st;
     if (n_out < 1) return fail(MKAMD_EINVAL, "n_out must be at least 1");
-    // the kept atoms' rows of [N][3][F] -> [3 n][F] -> frame-major [F][n][3] on the device
-    const size_t row = (size_t)3 * (size_t)F;
-    const float* src = coords;
-    if (keep) {
-        std::vector<float>& pk = ctx->packed_coords;
-        if (pk.size() < (size_t)n * row) pk.resize((size_t)n * row);
-        for (int64_t k = 0; k < n; ++k) std::memcpy(pk.data() + (size_t)k * row, coords + (size_t)keep[k] * row, row * sizeof(float));
-        src = pk.data();
-    }
-    void *dslab, *dxyz, *drad, *dmap, *dmask, *dout;
-    if ((st = upload(ctx, WS_S_SLAB, src, (size_t)n * row * 4, &dslab))) return st;
-    if ((st = ctx->ensure(WS_S_XYZ, (size_t)n * row * 4, &dxyz))) return st;
-    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dslab, 3 * n, F, F, 1.0f, (float*)dxyz))) return st;
+    // the kept atoms' rows of [N][3][F], in the caller's order (repeats included) -> [3 n][F] -> frame-major [F][n][3] on the device
+    if (keep) mkamd::gather_rows(coords, F, keep, n, ctx->packed_coords);
+    void *dxyz, *drad, *dmap, *dmask, *dout;
+    if ((st = upload_frame_major(ctx, WS_S_SLAB, WS_S_XYZ, keep ? ctx->packed_coords.data() : coords, 3 * n, F, &dxyz))) return st;
     if ((st = upload(ctx, WS_S_RADII, radii, (size_t)n * 4, &drad))) return st;
     if ((st = upload(ctx, WS_S_MAP, mapping, (size_t)n * 4, &dmap))) return st;
     if ((st = upload(ctx, WS_S_MASK, mask, (size_t)n * 4, &dmask))) return st;
@@ -2184,8 +2199,8 @@ try {
     std::string err;
     st = mkamd::run_sasa(*ctx, sasa_args((const float*)dxyz, n, F, (const float*)drad, n_points, (const int32_t*)dmap, (const int32_t*)dmask,
                                          coord_div, (float*)dout, n_out), err);
-    if (st) return err.empty() ? st : fail(st, err);
-    return ctx->to_host(out, dout, (size_t)F * n_out * 4);
+    if (st) return run_status(st, err);
+    return download(ctx, out, dout, (size_t)F * n_out * 4, false);
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------
@@ -2202,8 +2217,7 @@ try {
     std::string err;
     st = mkamd::run_shell_counts(*ctx, d_coords, F, d_box, d_sel1, n1, d_sel2, n2, d_chains, symmetric, pbc, d2_thresholds, n_edges,
                                  reinterpret_cast<int*>(d_counts), err, (ctx->dist_avoid >> 8) & 3);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 extern "C" int mkamd_shell_counts_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const float* box, const uint32_t* sel1, int64_t n1,
@@ -2219,34 +2233,21 @@ try {
         return MKAMD_OK;
     }
     if (!coords || !box || !sel1 || (n2 > 0 && !sel2) || !chains || !d2_thresholds || !counts) return fail(MKAMD_EINVAL, "NULL pointer");
-    for (int64_t i = 0; i < n1; ++i) if (sel1[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel1 index out of range");
-    for (int64_t i = 0; i < n2; ++i) if (sel2[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "sel2 index out of range");
+    if ((st = check_indices(sel1, n1, N, "sel1")) || (st = check_indices(sel2, n2, N, "sel2"))) return st;
     void *dc, *db, *d1, *d2, *dch, *dout;
-    // only the selected atoms' rows go up when they are few (host_pack.h); the selections and chain ids in the packed numbering
-    mkamd::PackedAtoms pk;
-    pk.collect(sel1, n1); pk.collect(sel2, n2);
-    int64_t rows = N;
-    if (!(ctx->dist_avoid & 32) && pk.finish(coords, N, F, ctx->packed_coords)) {
-        const std::vector<uint32_t> p1 = pk.remap(sel1, n1), p2 = pk.remap(sel2, n2), pc = pk.gather(chains);
-        rows = pk.size();
-        if ((st = upload(ctx, WS_H_COORDS, ctx->packed_coords.data(), (size_t)rows * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, p1.data(), (size_t)n1 * 4, &d1))) return st;
-        if ((st = upload(ctx, WS_D_SEL2, p2.data(), (size_t)n2 * 4, &d2))) return st;
-        if ((st = upload(ctx, WS_D_CHAINS, pc.data(), (size_t)rows * 4, &dch))) return st;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporaries above are read by then)
-    } else {
-        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)N * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, sel1, (size_t)n1 * 4, &d1))) return st;
-        if ((st = upload(ctx, WS_D_SEL2, sel2, (size_t)n2 * 4, &d2))) return st;
-        if ((st = upload(ctx, WS_D_CHAINS, chains, (size_t)N * 4, &dch))) return st;
-    }
+    HostStage up(ctx, coords, N, F, {{sel1, n1}, {sel2, n2}});
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.list_to(WS_D_SEL1, sel1, n1, &d1))) return st;
+    if ((st = up.list_to(WS_D_SEL2, sel2, n2, &d2))) return st;
+    if ((st = up.per_atom_to(WS_D_CHAINS, chains, &dch))) return st;
+    if ((st = up.sync())) return st;
     if ((st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
     const size_t bytes = (size_t)F * (size_t)n1 * (size_t)(n_edges - 1) * 4;
     if ((st = ctx->ensure(WS_H_OUT, bytes, &dout, 0))) return st;
-    st = mkamd_shell_counts_dev(ctx, (const float*)dc, rows, F, (const float*)db, (const uint32_t*)d1, n1, (const uint32_t*)d2, n2,
+    st = mkamd_shell_counts_dev(ctx, (const float*)dc, up.rows(), F, (const float*)db, (const uint32_t*)d1, n1, (const uint32_t*)d2, n2,
                                 (const uint32_t*)dch, symmetric, pbc, d2_thresholds, n_edges, (int32_t*)dout);
     if (st) return st;
-    return ctx->to_host(counts, dout, bytes);
+    return download(ctx, counts, dout, bytes, false);
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------
@@ -2262,8 +2263,7 @@ try {
     if (F > 0 && D > 0 && (!d_coords || !d_quads || !d_out)) return fail(MKAMD_EINVAL, "NULL pointer");
     std::string err;
     st = mkamd::run_dihedrals(*ctx, d_coords, F, d_box, d_box != nullptr, d_quads, D, mode, d_out, err, (ctx->dist_avoid >> 10) & 3);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 extern "C" int mkamd_dihedrals_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const float* box, int64_t n_box_frames,
@@ -2277,31 +2277,21 @@ try {
     if (F == 0 || D == 0) return MKAMD_OK;
     if (!coords || !quads || !out) return fail(MKAMD_EINVAL, "NULL pointer");
     if (F > 0x3fffffffLL || D > 0x3fffffffLL || (double)F * (double)D * (double)mkamd::dih_width(mode) >= 1.0e18) return fail(MKAMD_EINVAL, "result too large");
-    for (int64_t i = 0; i < 4 * D; ++i) if (quads[i] >= (uint64_t)N) return fail(MKAMD_EINVAL, "quads: atom index out of range");
+    if ((st = check_indices(quads, 4 * D, N, "quads: atom"))) return st;
     // the reference wraps only where the box is not all zeros (dihedral.py:dihedralAngle)
     bool wrap = false;
     if (box) for (int64_t i = 0; i < 3 * F && !wrap; ++i) wrap = !(box[i] == 0.0f);
     void *dc, *db = nullptr, *dq, *dout;
-    // only the rows of the atoms the quads name go up when they are few (host_pack.h); the quads in the packed numbering
-    mkamd::PackedAtoms pk;
-    pk.collect(quads, 4 * D);
-    int64_t rows = N;
-    if (!(ctx->dist_avoid & 32) && pk.finish(coords, N, F, ctx->packed_coords)) {
-        const std::vector<uint32_t> pq = pk.remap(quads, 4 * D);
-        rows = pk.size();
-        if ((st = upload(ctx, WS_H_COORDS, ctx->packed_coords.data(), (size_t)rows * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, pq.data(), (size_t)D * 16, &dq))) return st;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporary above is read by then)
-    } else {
-        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)N * 3 * F * 4, &dc))) return st;
-        if ((st = upload(ctx, WS_D_SEL1, quads, (size_t)D * 16, &dq))) return st;
-    }
+    HostStage up(ctx, coords, N, F, {{quads, 4 * D}});
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.list_to(WS_D_SEL1, quads, 4 * D, &dq))) return st;
+    if ((st = up.sync())) return st;
     if (wrap && (st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
     const size_t bytes = (size_t)F * (size_t)D * (size_t)mkamd::dih_width(mode) * 4;
     if ((st = ctx->ensure(WS_H_OUT, bytes, &dout, 0))) return st;
-    st = mkamd_dihedrals_dev(ctx, (const float*)dc, rows, F, (const float*)db, F, (const uint32_t*)dq, D, mode, (float*)dout);
+    st = mkamd_dihedrals_dev(ctx, (const float*)dc, up.rows(), F, (const float*)db, F, (const uint32_t*)dq, D, mode, (float*)dout);
     if (st) return st;
-    return ctx->to_host(out, dout, bytes);
+    return download(ctx, out, dout, bytes, false);
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------
@@ -2326,8 +2316,7 @@ try {
     std::string err;
     st = mkamd::run_group_moments(*ctx, mom_args(d_xyz, N, F, d_affine, d_atoms, d_offsets, d_weights, G, n_sel, max_group), mode, d_out, err,
                                   (ctx->dist_avoid >> 12) & 3);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 extern "C" int mkamd_fluctuation_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const double* d_affine, const uint32_t* d_atoms,
@@ -2338,8 +2327,7 @@ try {
     std::string err;
     st = mkamd::run_fluctuation(*ctx, mom_args(d_xyz, N, F, d_affine, d_atoms, d_offsets, nullptr, d_offsets ? G : 0, n_sel, d_offsets ? max_group : 1),
                                 d_ref, d_out, err, (ctx->dist_avoid >> 12) & 3);
-    if (st) return err.empty() ? st : fail(st, err);
-    return MKAMD_OK;
+    return run_status(st, err);
 } MK_API_CATCH
 
 // What the two host forms share: the rows of the atoms that `atoms` and `alnsel` name, packed ([M, 3, F]), uploaded and transposed to
@@ -2354,8 +2342,7 @@ static int mom_host_inputs(mkamd_ctx* ctx, const float* coords, int64_t N, int64
 {
     int st;
     if (!coords || !atoms || (alnsel && !alnref)) return fail(MKAMD_EINVAL, "NULL pointer");
-    for (int64_t k = 0; k < n_sel; ++k) if (atoms[k] >= (uint64_t)N) return fail(MKAMD_EINVAL, "atoms: atom index out of range");
-    for (int64_t k = 0; alnsel && k < n_aln; ++k) if (alnsel[k] >= (uint64_t)N) return fail(MKAMD_EINVAL, "alnsel: atom index out of range");
+    if ((st = check_indices(atoms, n_sel, N, "atoms: atom")) || (alnsel && (st = check_indices(alnsel, n_aln, N, "alnsel: atom")))) return st;
     if (offsets) {
         if (offsets[0] != 0 || (int64_t)offsets[G] != n_sel) return fail(MKAMD_EINVAL, "offsets must start at 0 and end at the number of group atoms");
         for (int64_t g = 0; g < G; ++g) {
@@ -2363,42 +2350,23 @@ static int mom_host_inputs(mkamd_ctx* ctx, const float* coords, int64_t N, int64
             in.max_group = std::max<int64_t>(in.max_group, (int64_t)offsets[g + 1] - (int64_t)offsets[g]);
         }
     }
-    mkamd::PackedAtoms pk;
-    pk.collect(atoms, n_sel);
-    if (alnsel) pk.collect(alnsel, n_aln);
-    std::sort(pk.uniq.begin(), pk.uniq.end());
-    pk.uniq.erase(std::unique(pk.uniq.begin(), pk.uniq.end()), pk.uniq.end());
-    const int64_t M = pk.size();
-    const size_t row = (size_t)3 * (size_t)F;
-    std::vector<float>& pc = ctx->packed_coords;
-    if (pc.size() < (size_t)M * row) pc.resize((size_t)M * row);
-    for (int64_t k = 0; k < M; ++k) std::memcpy(pc.data() + (size_t)k * row, coords + (size_t)pk.uniq[(size_t)k] * row, row * sizeof(float));
-    in.rows = M;
-    void* dslab;
-    if ((st = upload(ctx, WS_A_SLAB, pc.data(), (size_t)M * row * 4, &dslab))) return st;
-    if ((st = ctx->ensure(WS_A_XYZ, (size_t)M * row * 4, &in.dxyz))) return st;
-    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dslab, 3 * M, F, F, 1.0f, (float*)in.dxyz))) return st;
-    const std::vector<uint32_t> pa = pk.remap(atoms, n_sel);
-    if ((st = upload(ctx, WS_M_ATOMS, pa.data(), (size_t)n_sel * 4, &in.datoms))) return st;
+    HostStage up(ctx, coords, N, F, {{atoms, n_sel}, {alnsel, n_aln}}, /*always=*/true);
+    in.rows = up.rows();
+    if ((st = upload_frame_major(ctx, WS_A_SLAB, WS_A_XYZ, up.host_rows(), 3 * in.rows, F, &in.dxyz))) return st;
+    if ((st = up.list_to(WS_M_ATOMS, atoms, n_sel, &in.datoms))) return st;
     if (offsets && (st = upload(ctx, WS_M_OFFS, offsets, (size_t)(G + 1) * 4, &in.doffs))) return st;
     if (weights && (st = upload(ctx, WS_M_W, weights, (size_t)n_sel * 4, &in.dw))) return st;
-    if (alnsel) {
-        const std::vector<uint32_t> ps = pk.remap(alnsel, n_aln);
-        std::vector<uint32_t> rs((size_t)n_aln);
-        for (int64_t k = 0; k < n_aln; ++k) rs[(size_t)k] = (uint32_t)k;
-        void *dsel, *drefsel, *dref;
-        if ((st = upload(ctx, WS_A_SEL, ps.data(), (size_t)n_aln * 4, &dsel))) return st;
-        if ((st = upload(ctx, WS_A_REFSEL, rs.data(), (size_t)n_aln * 4, &drefsel))) return st;
-        if ((st = upload(ctx, WS_A_REF, alnref, (size_t)n_aln * 12, &dref))) return st;
-        if ((st = ctx->ensure(WS_A_AFFINE, (size_t)F * 12 * 8, &in.daff))) return st;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                  // (the temporaries above are read by then)
-        if ((st = mkamd_align_transforms_dev(ctx, (const float*)in.dxyz, M, F, (const float*)dref, n_aln, 1, (const uint32_t*)dsel,
-                                             (const uint32_t*)drefsel, n_aln, nullptr, F, 0, 0, (double*)in.daff, nullptr)))
-            return st;
-    } else {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return MKAMD_OK;
+    if (!alnsel) return up.sync();
+    std::vector<uint32_t> rs((size_t)n_aln);
+    for (int64_t k = 0; k < n_aln; ++k) rs[(size_t)k] = (uint32_t)k;
+    void *dsel, *drefsel, *dref;
+    if ((st = up.list_to(WS_A_SEL, alnsel, n_aln, &dsel))) return st;
+    if ((st = upload(ctx, WS_A_REFSEL, rs.data(), (size_t)n_aln * 4, &drefsel))) return st;
+    if ((st = upload(ctx, WS_A_REF, alnref, (size_t)n_aln * 12, &dref))) return st;
+    if ((st = ctx->ensure(WS_A_AFFINE, (size_t)F * 12 * 8, &in.daff))) return st;
+    if ((st = up.sync())) return st;                                 // (rs is read by then as well)
+    return mkamd_align_transforms_dev(ctx, (const float*)in.dxyz, in.rows, F, (const float*)dref, n_aln, 1, (const uint32_t*)dsel,
+                                      (const uint32_t*)drefsel, n_aln, nullptr, F, 0, 0, (double*)in.daff, nullptr);
 }
 
 extern "C" int mkamd_group_moments_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* alnsel, const float* alnref,
@@ -2421,7 +2389,7 @@ try {
     st = mkamd_group_moments_dev(ctx, (const float*)in.dxyz, in.rows, F, (const double*)in.daff, (const uint32_t*)in.datoms, (const uint32_t*)in.doffs,
                                  (const float*)in.dw, G, n_sel, in.max_group, mode, (float*)dout);
     if (st) return st;
-    return ctx->to_host(out, dout, bytes);
+    return download(ctx, out, dout, bytes, false);
 } MK_API_CATCH
 
 extern "C" int mkamd_fluctuation_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* alnsel, const float* alnref,
@@ -2445,7 +2413,7 @@ try {
     st = mkamd_fluctuation_dev(ctx, (const float*)in.dxyz, in.rows, F, (const double*)in.daff, (const uint32_t*)in.datoms, n_sel,
                                (const uint32_t*)in.doffs, G, in.max_group, (const double*)dref, (double*)dout);
     if (st) return st;
-    return ctx->to_host(out, dout, bytes);
+    return download(ctx, out, dout, bytes, false);
 } MK_API_CATCH
 
 #ifdef MK_PHASE_TIMERS

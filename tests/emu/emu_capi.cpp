@@ -466,14 +466,15 @@ int emu_contacts(const float* coords, long long F, const float* box, const unsig
 }
 
 // csrc/host_pack.h as the host entry points use it: returns 1 when the call would upload the packed rows (then out_coords [M,3,F], out_uniq [M],
-// out_remap [n] = the selection in the packed numbering are filled), 0 when the array goes up as it is (out_uniq / *M still say which atoms)
+// out_remap [n] = the selection in the packed numbering are filled), 0 when the array goes up as it is (out_uniq / *M still say which atoms);
+// `always`: the form that packs whatever the sizes (group moments)
 int emu_pack_atoms(const float* coords, long long N, long long F, const unsigned* sel, long long n, float* out_coords, unsigned* out_uniq,
-                   unsigned* out_remap, long long* M)
+                   unsigned* out_remap, long long* M, int always)
 {
     PackedAtoms pk;
     pk.collect(sel, n);
     std::vector<float> buf;
-    const bool on = pk.finish(coords, N, F, buf);
+    const bool on = pk.finish(coords, N, F, buf, always != 0);
     *M = pk.size();
     for (long long k = 0; k < pk.size(); ++k) out_uniq[k] = pk.uniq[(size_t)k];
     if (!on) return 0;
@@ -481,6 +482,14 @@ int emu_pack_atoms(const float* coords, long long N, long long F, const unsigned
     const std::vector<unsigned> r = pk.remap(sel, n);
     for (long long i = 0; i < n; ++i) out_remap[i] = r[(size_t)i];
     return 1;
+}
+
+// the row gather on its own (the surface-area call's kept atoms): rows idx[0..n) in the order given into out [n,3,F]
+void emu_gather_rows(const float* coords, long long F, const unsigned* idx, long long n, float* out)
+{
+    std::vector<float> buf;
+    gather_rows(coords, F, idx, n, buf);
+    memcpy(out, buf.data(), (size_t)n * 3 * (size_t)F * sizeof(float));
 }
 
 void emu_unpack_atoms(const unsigned* uniq, long long M, unsigned* atoms, long long n)

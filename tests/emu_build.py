@@ -244,9 +244,10 @@ def contacts_trajectory(coords, box, sel1, sel2, chains, selfdist, pbc, threshol
     return [flat[2 * offs[f]:2 * offs[f + 1]].tolist() for f in range(F)]
 
 
-def pack_atoms(coords, sels, per_atom=None):
+def pack_atoms(coords, sels, per_atom=None, always=False):
     """csrc/host_pack.h (what the library's host entry points of the distance functions do before the upload): -> (on, uniq, packed coords
-    [M, 3, F], the selections in the packed numbering, `per_atom` gathered) for selections `sels` (a list of index arrays)."""
+    [M, 3, F], the selections in the packed numbering, `per_atom` gathered) for selections `sels` (a list of index arrays); `always`: the
+    form that packs whatever the sizes."""
     coords = np.ascontiguousarray(coords, np.float32)
     N, _, F = coords.shape
     flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.uint32).ravel() for s in sels]) if sels else np.zeros(0, np.uint32), np.uint32)
@@ -255,12 +256,21 @@ def pack_atoms(coords, sels, per_atom=None):
     remap = np.zeros(max(len(flat), 1), np.uint32)
     M = ctypes.c_longlong(0)
     on = lib().emu_pack_atoms(_p(coords), ctypes.c_longlong(N), ctypes.c_longlong(F), _p(flat), ctypes.c_longlong(len(flat)), _p(out), _p(uniq), _p(remap),
-                              ctypes.byref(M))
+                              ctypes.byref(M), ctypes.c_int(int(always)))
     m = M.value
     back = remap[:len(flat)].copy()
     if on:
         lib().emu_unpack_atoms(_p(uniq), ctypes.c_longlong(m), _p(back), ctypes.c_longlong(len(back)))
     return bool(on), uniq[:m].copy(), out[:m].copy(), remap[:len(flat)].copy(), back
+
+
+def gather_rows(coords, idx):
+    """csrc/host_pack.h gather_rows: rows `idx` of coords [N, 3, F] in the order given -> [n, 3, F]"""
+    coords = np.ascontiguousarray(coords, np.float32)
+    idx = np.ascontiguousarray(idx, np.uint32)
+    out = np.full((len(idx), 3, coords.shape[2]), np.nan, np.float32)
+    lib().emu_gather_rows(_p(coords), ctypes.c_longlong(coords.shape[2]), _p(idx), ctypes.c_longlong(len(idx)), _p(out))
+    return out
 
 
 def cdist(c1, c2):

@@ -798,6 +798,22 @@ def test_host_calls_pack_the_selected_atoms_before_the_upload():
     assert on and uniq.tolist() == [5] and np.array_equal(packed[0], c[5])
 
 
+def test_host_pack_always_form_and_the_gather_that_keeps_the_callers_order():
+    """csrc/host_pack.h: the form that packs whatever the sizes (group moments) on an array of less than a megabyte that the deciding
+    form leaves as it is; and the row gather on its own (the surface-area call's kept atoms): the caller's order, repeats included."""
+    rng = np.random.default_rng(17)
+    c = rng.normal(size=(3000, 3, 40)).astype(np.float32)[:, :, :20].copy()     # 0.72 MB
+    s1 = rng.integers(0, 3000, size=200).astype(np.uint32)
+    s2 = rng.permutation(3000)[:900].astype(np.uint32)           # with s1: more than a quarter of the atoms
+    flat = np.concatenate([s1, s2])
+    assert not E.pack_atoms(c, [s1, s2])[0]
+    on, uniq, packed, remap, back = E.pack_atoms(c, [s1, s2], always=True)
+    assert on and len(uniq) * 4 > 3000 and np.array_equal(uniq, np.unique(flat))
+    assert np.array_equal(packed, c[uniq.astype(np.int64)])
+    assert np.array_equal(uniq[remap.astype(np.int64)], flat) and np.array_equal(back, flat)
+    assert np.array_equal(E.gather_rows(c, [7, 3, 7, 0]), c[[7, 3, 7, 0]])
+
+
 def test_selfdist_of_few_frames_goes_through_the_triangular_row_kernel():
     """Round 6 (late): a selfdist call of large selections (>= 700 atoms up to 32 frames, >= 1 500 at any frame count) takes the row kernel's triangular
     form (k_dist_rows<.., TRI>: lanes along the second atoms, tasks below the diagonal skipped, the reference's condensed order written

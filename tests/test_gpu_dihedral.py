@@ -74,6 +74,31 @@ def test_terms_bit_equal_every_case_both_kernels_both_routes(ctx, real):
     assert C.bit_equal(R.terms(mol.coords, quads), t)
 
 
+def test_host_route_packed_and_whole_array_uploads_bit_equal(ctx):
+    """The host route uploads only the rows of the atoms the quads name when those are at most a quarter of a > 1-MB array
+    (csrc/host_pack.h; smaller arrays never pack): 150 quads drawn unsorted and with repeats from 600 of 3000 atoms, 40 frames
+    (1.44 MB), with and without a box -- packed (mask 0) and with the whole array uploaded (avoid bit 32), the restatement's bits."""
+    from moleculekit_amd.dihedral import dihedrals
+    rng = np.random.default_rng(61)
+    N, F = 3000, 40
+    box = (np.array([20.0, 24.0, 16.0])[:, None] + rng.uniform(-1, 1, size=(3, F))).astype(F32)
+    steps = rng.normal(size=(N, 3, F))
+    walk = np.cumsum(steps * (1.5 / np.linalg.norm(steps, axis=1, keepdims=True)), axis=0)
+    coords = np.ascontiguousarray((walk - np.floor(walk / box[None]) * box[None]).astype(F32))
+    quads = rng.permutation(N)[:600][rng.integers(0, 600, size=(150, 4))].astype(U32)
+    named = np.unique(quads)
+    assert len(named) * 4 <= N and len(named) < quads.size and np.any(np.diff(quads.ravel().astype(np.int64)) < 0)
+    for b in (None, box):
+        want = R.terms(coords, quads, b)
+        for mask in (0, 32):
+            ctx.set_dist_kernels(mask)
+            try:
+                got = dihedrals(coords, quads, box=b, out="terms", ctx=ctx)
+            finally:
+                ctx.set_dist_kernels(0)
+            assert got.shape == want.shape and C.bit_equal(got, want), (b is not None, mask)
+
+
 def test_plan_chooses_by_frames(ctx):
     for F, name in ((1, "k_dihedral_atoms"), (63, "k_dihedral_atoms"), (64, "k_dihedral_frames"), (200, "k_dihedral_frames")):
         coords, quads = C.random_case(40, 33, F, 5)

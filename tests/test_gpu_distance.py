@@ -758,8 +758,9 @@ def test_host_calls_that_pack_the_selected_atoms_equal_the_unpacked_calls():
     """csrc/host_pack.h (round 6): a host call whose selections are at most a quarter of a > 1-MB coordinate array uploads only the
     selected atoms' rows, in a packed numbering.  Unsorted selections with repeats, chain ids and masses gathered, contact lists
     translated back to the caller's atom numbers: dist_trajectory, contacts_trajectory and the group reductions (closest atom and
-    centre of mass) against the oracle on the whole array, bit for bit."""
-    from moleculekit_amd import distance_utils as du
+    centre of mass) against the oracle on the whole array, bit for bit -- and the same calls with avoid bit 32 set, which upload the
+    whole array: both routes of the one staging path (capi.hip: HostStage)."""
+    from moleculekit_amd import _lib, distance_utils as du
     rng = np.random.default_rng(29)
     N, F = 3000, 40                                              # 1.44 MB: packed
     c = rng.uniform(0, 40.0, size=(N, 3, F)).astype(np.float32)
@@ -768,32 +769,40 @@ def test_host_calls_that_pack_the_selected_atoms_equal_the_unpacked_calls():
     m = rng.uniform(1, 32, size=N).astype(np.float32)
     s1 = rng.integers(0, N, size=130).astype(np.uint32); s1[5] = s1[6]          # unsorted, a repeat
     s2 = rng.permutation(N)[:70].astype(np.uint32)
-    for selfd, a, bb in ((False, s1, s2), (True, s2, s2)):
-        for pbc in (True, False):
-            exp = oracle.dist_trajectory(c, b, a, bb, ch, selfd, pbc)
-            got = np.full_like(exp, -1.0)
-            du.dist_trajectory(c, b, a, bb, ch, selfd, pbc, got)
-            assert np.array_equal(got, exp), (selfd, pbc)
-        d2 = oracle.dist_trajectory(c, b, a, bb, ch, selfd, True, squared=True)
-        table = ([(a[i], bb[j]) for i in range(len(a)) for j in range(i + 1, len(bb))] if selfd else
-                 [(a[i], bb[j]) for i in range(len(a)) for j in range(len(bb))])
-        lists = du.contacts_trajectory(c, b, a, bb, ch, selfd, True, 9.0)
-        n_hits = 0
-        for f in range(F):
-            hits = np.nonzero(d2[f] <= np.float32(81.0))[0]
-            assert lists[f] == [int(v) for k in hits for v in table[k]], (selfd, f)
-            n_hits += len(hits)
-        assert n_hits > 50
     atoms = rng.permutation(N)[:240]
     g1 = [list(map(int, atoms[i * 8:(i + 1) * 8])) for i in range(12)]
     g2 = [list(map(int, atoms[96 + i * 9:96 + (i + 1) * 9])) for i in range(16)]
     c1 = rng.integers(0, 3, size=12).astype(np.uint32); c2 = rng.integers(0, 3, size=16).astype(np.uint32)
+    # the oracle's results, once; then the library's under both masks
+    dist_cases, contact_cases, red_cases = [], [], []
+    for selfd, a, bb in ((False, s1, s2), (True, s2, s2)):
+        dist_cases += [(a, bb, selfd, pbc, oracle.dist_trajectory(c, b, a, bb, ch, selfd, pbc)) for pbc in (True, False)]
+        d2 = oracle.dist_trajectory(c, b, a, bb, ch, selfd, True, squared=True)
+        table = ([(a[i], bb[j]) for i in range(len(a)) for j in range(i + 1, len(bb))] if selfd else
+                 [(a[i], bb[j]) for i in range(len(a)) for j in range(len(bb))])
+        want = [[int(v) for k in np.nonzero(d2[f] <= np.float32(81.0))[0] for v in table[k]] for f in range(F)]
+        assert sum(len(w) for w in want) // 2 > 50
+        contact_cases.append((a, bb, selfd, want))
     for r1, r2 in ((0, 0), (1, 1), (0, 1)):
-        for pbc in (True, False):
-            exp = oracle.dist_trajectory_reduction(c, b, g1, g2, c1, c2, False, pbc, m, r1, r2)
-            got = np.full_like(exp, -1.0)
-            du.dist_trajectory_reduction(c, b, g1, g2, c1, c2, False, pbc, m, r1, r2, got)
-            assert np.array_equal(got, exp), (r1, r2, pbc)
+        red_cases += [(r1, r2, pbc, oracle.dist_trajectory_reduction(c, b, g1, g2, c1, c2, False, pbc, m, r1, r2)) for pbc in (True, False)]
+    ctx = _lib.default_context()
+    try:
+        for mask in (0, 32):
+            ctx.set_dist_kernels(mask)
+            for a, bb, selfd, pbc, exp in dist_cases:
+                got = np.full_like(exp, -1.0)
+                du.dist_trajectory(c, b, a, bb, ch, selfd, pbc, got)
+                assert np.array_equal(got, exp), (mask, selfd, pbc)
+            for a, bb, selfd, want in contact_cases:
+                lists = du.contacts_trajectory(c, b, a, bb, ch, selfd, True, 9.0)
+                for f in range(F):
+                    assert lists[f] == want[f], (mask, selfd, f)
+            for r1, r2, pbc, exp in red_cases:
+                got = np.full_like(exp, -1.0)
+                du.dist_trajectory_reduction(c, b, g1, g2, c1, c2, False, pbc, m, r1, r2, got)
+                assert np.array_equal(got, exp), (mask, r1, r2, pbc)
+    finally:
+        ctx.set_dist_kernels(0)
 
 
 def test_reductions_of_few_frames_take_lanes_along_the_second_groups():
