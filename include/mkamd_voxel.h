@@ -128,6 +128,12 @@ int mkamd_ctx_set_tile_items(mkamd_ctx* ctx, int mode);
  * atoms in slices of 2 048, joined by an atomic maximum); -1 = they are recomputed inside the last launch, one wave per value over
  * all of the item's atoms (rounds 3-5; what every other kind of call does).  Results are bit-identical either way. */
 int mkamd_ctx_set_exact_redo(mkamd_ctx* ctx, int mode);
+/* The cover fold of a call that bins through a TOPOLOGY handle (frame or batch): 0 (default) = an atom that channel 7 of its
+ * channel group holds with the same sigma as one of the group's channels 0..6 (the reference's `occupancies` channel: every heavy
+ * atom at its vdW radius) is tested against a tile's voxels once, not twice -- the other channel's class minimum goes into channel
+ * 7 as well (mkamd_topology_cover_mask says for which sigma classes the handle's atoms allow that); -1 = every channel keeps its
+ * full lists (tests and A-B timing).  Results are bit-identical either way. */
+int mkamd_ctx_set_cover_fold(mkamd_ctx* ctx, int mode);
 /* Opt-in software pipelining ACROSS calls of mkamd_voxelize_lattice_dev (off by default): the binning
  * pre-pass of a call (latency / atomic bound) runs on an internal stream beside the tile kernel (VALU bound)
  * of the previous call, on a second workspace set.  Results still appear in order on the context's stream.
@@ -280,6 +286,10 @@ int mkamd_topology_create_host(mkamd_ctx* ctx, const void* sigmas, int sigmas_ar
 /* Waits for the context's streams (calls that read the handle), then frees it.  ctx may be NULL (the whole device is drained). */
 int mkamd_topology_destroy(mkamd_ctx* ctx, mkamd_topology* topology);
 int mkamd_topology_info(const mkamd_topology* topology, int64_t* n_atoms, int32_t* n_channels, double* voxelsize, int32_t* has_wide_sigmas);
+/* The sigma classes (bit s = class id s, 1..15, in the order of the handle's class table) that channel 7 of channel group `group`
+ * COVERS: every atom of the handle that has class s in one of the group's channels 0..6 has it in channel 7 too.  Classes that no
+ * atom carries in channels 0..6 are covered trivially; bit 0 is always clear.  See mkamd_ctx_set_cover_fold. */
+int mkamd_topology_cover_mask(const mkamd_topology* topology, int32_t group, uint32_t* mask);
 int mkamd_voxelize_lattice_topo_dev(mkamd_ctx* ctx, int32_t n_items, const float* d_coords, const int64_t* d_atom_offsets,
                                     int64_t total_atoms, const mkamd_topology* topology, const double* d_origins,
                                     const int32_t* nvoxels, double voxelsize, const float* d_box, int32_t max_images_per_atom,

@@ -56,6 +56,7 @@ SIGNATURES = {
     "mkamd_ctx_set_tile_team": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_tile_items": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_exact_redo": (_c_int, [_vp, _c_int]),
+    "mkamd_ctx_set_cover_fold": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_fine_cells": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_value_tolerance": (_c_int, [_vp, ctypes.c_double]),
     "mkamd_ctx_set_direct_binning": (_c_int, [_vp, _c_int]),
@@ -80,6 +81,7 @@ SIGNATURES = {
     "mkamd_topology_create_host": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i32, _c_dbl, ctypes.POINTER(_vp)]),
     "mkamd_topology_destroy": (_c_int, [_vp, _vp]),
     "mkamd_topology_info": (_c_int, [_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i32), ctypes.POINTER(_c_dbl), ctypes.POINTER(_c_i32)]),
+    "mkamd_topology_cover_mask": (_c_int, [_vp, _c_i32, ctypes.POINTER(ctypes.c_uint32)]),
     "mkamd_voxelize_lattice_topo_dev": (_c_int, [_vp, _c_i32, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_dbl, _vp, _c_i32, _vp, _vp]),
     "mkamd_topology_create_batch_dev": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i32, _c_dbl, _vp, _c_i32, ctypes.POINTER(_vp)]),
     "mkamd_topology_create_batch_host": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i32, _c_dbl, _vp, _c_i32, ctypes.POINTER(_vp)]),
@@ -303,6 +305,11 @@ class Context:
         """0 (default): a topology call with wide sigmas hands its exact cut-off hits to a launch of their own (many waves per value);
         -1: recomputed inside the call's last launch (include/mkamd_voxel.h).  Same bits either way."""
         _check(load().mkamd_ctx_set_exact_redo(self._h, int(mode)))
+
+    def set_cover_fold(self, mode: int = 0):
+        """0 (default): a call that bins through a topology handle tests an atom once where channel 7 of its group holds it with the
+        sigma of another channel; -1: every channel keeps its full lists (include/mkamd_voxel.h).  Same bits either way."""
+        _check(load().mkamd_ctx_set_cover_fold(self._h, int(mode)))
 
     def set_fine_cells(self, on: bool):
         """Half-cutoff cells instead of cutoff-sized ones (A-B benchmarking; same values to float32 noise)."""
@@ -585,6 +592,12 @@ class Topology:
         w = _c_i32(0)
         _check(load().mkamd_topology_info(self._h, None, None, None, ctypes.byref(w)))
         return bool(w.value)
+
+    def cover_mask(self, group: int = 0) -> int:
+        """The sigma classes (bit s = class id s) that channel 7 of channel group ``group`` covers (include/mkamd_voxel.h)."""
+        m = ctypes.c_uint32(0)
+        _check(load().mkamd_topology_cover_mask(self._h, int(group), ctypes.byref(m)))
+        return int(m.value)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

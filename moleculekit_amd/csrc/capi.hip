@@ -97,6 +97,7 @@ struct mkamd_ctx {
     int prepass_mode = -1;                 // -1 = automatic
     int tile_items = -1;                   // -1 = automatic
     int exact_redo = 0;                    // 0 = automatic (mkamd_ctx_set_exact_redo), -1 = never
+    int cover_fold = 0;                    // 0 = automatic (mkamd_ctx_set_cover_fold), -1 = never
     int tile_team = -1;                    // -1 = automatic
     int fine_cells = 0;                    // 1 = half-cutoff cells (A-B benchmarking)
     int direct = -1;                       // direct binning: -1 automatic, 0 never, 1 whenever possible (mkamd_ctx_set_direct_binning)
@@ -309,8 +310,9 @@ struct mkamd_ctx {
 // A molecule's topology on the device (include/mkamd_voxel.h, mkamd_topology_create_*): one allocation, owned here.
 struct mkamd_topology {
     int device = 0;
-    void* mem = nullptr;                   // sigmas copy | cw | ids | table | flags | wide list | atom offsets (a batch handle)
+    void* mem = nullptr;                   // sigmas copy | cw | ids | table | flags + violated-class words | wide list | atom offsets (a batch handle)
     mkamd::TopologyDev dev;
+    std::vector<unsigned> h_cover;         // per channel group: the classes its channel 7 covers (dev.h_cover)
     std::vector<long long> h_offsets;      // a batch handle: its atom offsets and its wide list on the host (dev.h_offsets, dev.h_wide_list)
     std::vector<unsigned> h_wide;
 };
@@ -566,6 +568,14 @@ try {
     if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
     if (mode != 0 && mode != -1) return fail(MKAMD_EINVAL, "exact redo mode must be 0 (automatic) or -1 (recompute inside the last launch)");
     ctx->exact_redo = mode;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+int mkamd_ctx_set_cover_fold(mkamd_ctx* ctx, int mode)
+try {
+    if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
+    if (mode != 0 && mode != -1) return fail(MKAMD_EINVAL, "cover fold mode must be 0 (automatic) or -1 (every channel keeps its full lists)");
+    ctx->cover_fold = mode;
     return MKAMD_OK;
 } MK_API_CATCH
 
@@ -905,7 +915,7 @@ static int voxelize_lattice_dev_impl(mkamd_ctx* ctx, int32_t B, const float* d_c
     P.B = B; P.total_atoms = total_atoms; P.C = C; P.sigmas_f64 = sigmas_are_f64;
     P.nvox[0] = nvoxels[0]; P.nvox[1] = nvoxels[1]; P.nvox[2] = nvoxels[2];
     P.voxelsize = voxelsize; P.pbc = d_box ? 1 : 0; P.max_images = d_box ? max_images : 1;
-    P.tile_k = ctx->tile_k; P.force_general = ctx->force_general; P.lds_tier = ctx->lds_tier; P.prepass_mode = ctx->prepass_mode; P.tile_team = ctx->tile_team; P.tile_items = ctx->tile_items; P.exact_redo_list = ctx->exact_redo; P.fine_cells = ctx->fine_cells; P.value_tol = ctx->value_tol; P.direct = ctx->direct; P.seq = ctx->seq_next; ctx->seq_next = 0u;
+    P.tile_k = ctx->tile_k; P.force_general = ctx->force_general; P.lds_tier = ctx->lds_tier; P.prepass_mode = ctx->prepass_mode; P.tile_team = ctx->tile_team; P.tile_items = ctx->tile_items; P.exact_redo_list = ctx->exact_redo; P.cover_fold = ctx->cover_fold; P.fine_cells = ctx->fine_cells; P.value_tol = ctx->value_tol; P.direct = ctx->direct; P.seq = ctx->seq_next; ctx->seq_next = 0u;
     P.coords = d_coords; P.atom_offsets = (const long long*)d_atom_offsets; P.sigmas = d_sigmas;
     P.origins = d_origins; P.box = d_box; P.affine = d_affine; P.out = d_features;
     P.topo = topo ? &topo->dev : nullptr;
@@ -952,7 +962,9 @@ static int topology_create_impl(mkamd_ctx* ctx, const void* d_sigmas, int sigmas
     const int G = ceil_div(C, CHG);
     const size_t a256 = 255, sig_bytes = (size_t)n_atoms * C * (sigmas_are_f64 ? 8 : 4);
     const size_t o_cw = (sig_bytes + a256) & ~a256, o_ids = (o_cw + (size_t)n_atoms * G * sizeof(uint2) + a256) & ~a256,
-                 o_tab = (o_ids + (size_t)n_atoms * G * sizeof(unsigned) + a256) & ~a256, o_flags = o_tab + 256, o_wide = o_flags + 256,
+                 o_tab = (o_ids + (size_t)n_atoms * G * sizeof(unsigned) + a256) & ~a256, o_flags = o_tab + 256,
+                 flag_bytes = (8 + (size_t)G * sizeof(unsigned) + a256) & ~a256,       // flags [2], then the violated-class words [G]
+                 o_wide = o_flags + flag_bytes,
                  o_offs = (o_wide + (size_t)n_atoms * sizeof(unsigned) + a256) & ~a256,
                  total = o_offs + (h_offsets ? (size_t)n_items + 1 : 0) * sizeof(long long);
     mkamd_topology* t = new mkamd_topology();
@@ -962,18 +974,20 @@ static int topology_create_impl(mkamd_ctx* ctx, const void* d_sigmas, int sigmas
     char* m = (char*)t->mem;
     auto drop = [&](int code) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(t->mem); delete t; return code; };
     if ((e = hipMemcpyAsync(m, d_sigmas, sig_bytes, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) return drop(hip_fail(e, "hipMemcpyAsync(topology sigmas)"));
-    if ((e = hipMemsetAsync(m + o_flags, 0, 256, ctx->stream)) != hipSuccess) return drop(hip_fail(e, "hipMemsetAsync(topology flags)"));
+    if ((e = hipMemsetAsync(m + o_flags, 0, flag_bytes, ctx->stream)) != hipSuccess) return drop(hip_fail(e, "hipMemsetAsync(topology flags)"));
     std::string err;
     st = run_topology_build(*ctx, m, sigmas_are_f64, (long long)n_atoms, C, voxelsize, (uint2*)(m + o_cw), (unsigned*)(m + o_ids),
-                            (unsigned*)(m + o_tab), (int*)(m + o_flags), (unsigned*)(m + o_wide), err);
+                            (unsigned*)(m + o_tab), (int*)(m + o_flags), (unsigned*)(m + o_wide), err, (unsigned*)(m + o_flags + 8));
     if (st) return drop(run_status(st, err));
     unsigned table[CLS_TABLE_WORDS];
-    int flags2[2] = {0, 0};
+    std::vector<unsigned> fl(2 + (size_t)G, 0u);                     // the flags and the violated-class words: one read-back
     if ((e = hipMemcpyAsync(table, m + o_tab, sizeof table, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(flags2, m + o_flags, sizeof flags2, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(fl.data(), m + o_flags, fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return drop(hip_fail(e, "topology read-back"));
-    const int flags = flags2[0];
-    const unsigned n_wide = (unsigned)flags2[1];
+    const int flags = (int)fl[0];
+    const unsigned n_wide = fl[1];
+    t->h_cover.resize((size_t)G);
+    for (int gq = 0; gq < G; ++gq) t->h_cover[gq] = ~fl[2 + gq] & 0xfffeu;
     std::vector<unsigned>& wl = t->h_wide;                           // (a batch handle keeps the list on the host too)
     wl.resize(n_wide);
     if (n_wide > 1u || (n_wide != 0u && h_offsets)) {
@@ -990,6 +1004,7 @@ static int topology_create_impl(mkamd_ctx* ctx, const void* d_sigmas, int sigmas
     t->dev.sigmas = m; t->dev.cw = (const uint2*)(m + o_cw); t->dev.ids = (const unsigned*)(m + o_ids); t->dev.table = (const unsigned*)(m + o_tab);
     t->dev.overflow = false; t->dev.wide = (flags & 1) != 0;
     t->dev.wide_list = (const unsigned*)(m + o_wide); t->dev.n_wide = n_wide;
+    t->dev.cover_violated = (const unsigned*)(m + o_flags + 8); t->dev.h_cover = t->h_cover.data();
     if (h_offsets) {
         t->h_offsets.assign(h_offsets, h_offsets + n_items + 1);
         if ((e = hipMemcpyAsync(m + o_offs, t->h_offsets.data(), ((size_t)n_items + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
@@ -1090,6 +1105,14 @@ try {
                                      voxelsize, d_box, max_images, d_affine, d_features, topo, first_item);
 } MK_API_CATCH
 
+int mkamd_topology_cover_mask(const mkamd_topology* topo, int32_t group, uint32_t* mask)
+try {
+    if (!topo || !mask) return fail(MKAMD_EINVAL, "topology / mask is NULL");
+    if (group < 0 || group >= topo->dev.G) return fail(MKAMD_EINVAL, "not a channel group of the topology");
+    *mask = topo->h_cover[(size_t)group];
+    return MKAMD_OK;
+} MK_API_CATCH
+
 int mkamd_topology_batch_info(const mkamd_topology* topo, int32_t* n_items, int64_t* longest_item)
 try {
     if (!topo) return fail(MKAMD_EINVAL, "topology is NULL");
@@ -1113,7 +1136,7 @@ try {
     P.B = n_items; P.total_atoms = t.h_offsets[first_item + n_items] - t.h_offsets[first_item]; P.C = t.C; P.sigmas_f64 = t.sigmas_f64;
     P.nvox[0] = nvoxels[0]; P.nvox[1] = nvoxels[1]; P.nvox[2] = nvoxels[2];
     P.voxelsize = t.voxelsize; P.pbc = periodic ? 1 : 0; P.max_images = periodic ? max_images : 1;
-    P.tile_k = ctx->tile_k; P.force_general = ctx->force_general; P.lds_tier = ctx->lds_tier; P.prepass_mode = ctx->prepass_mode; P.tile_team = ctx->tile_team; P.tile_items = ctx->tile_items; P.exact_redo_list = ctx->exact_redo; P.fine_cells = ctx->fine_cells; P.value_tol = ctx->value_tol; P.direct = ctx->direct;
+    P.tile_k = ctx->tile_k; P.force_general = ctx->force_general; P.lds_tier = ctx->lds_tier; P.prepass_mode = ctx->prepass_mode; P.tile_team = ctx->tile_team; P.tile_items = ctx->tile_items; P.exact_redo_list = ctx->exact_redo; P.cover_fold = ctx->cover_fold; P.fine_cells = ctx->fine_cells; P.value_tol = ctx->value_tol; P.direct = ctx->direct;
     P.topo = &t; P.topo_first_item = first_item;
     GridDesc g;
     std::string err;

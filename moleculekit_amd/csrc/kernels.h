@@ -119,7 +119,29 @@ struct GridDesc {
     // longest item of the handle (k_exact_redo's slices) and topo_wide the wide atoms inside the range (the fix-up's jobs).
     const long long* topo_offsets;
     long long topo_base;
+    // cover fold (round 8; voxelize_tile, "cover"): != nullptr -- the call bins through a handle whose build (k_topology_ids) left
+    // one word per channel group: bit s set = some atom of the handle has class s in a channel 0..6 of the group and NOT in its
+    // channel 7.  The classes whose bit is clear are COVERED by channel 7; the sorted tile path tests their atoms once.  One
+    // launch serves every group (blockIdx.y), hence the words and not one mask; nullptr = off: every other construction of a
+    // GridDesc (plain, direct-binning, per-item, one-molecule calls) keeps the full lists.
+    const unsigned* cover_violated;
 };
+// The classes of channel group gq that its channel 7 covers, as a mask over class ids 1..15 (bit 0 stays clear: nibble 0 = absent).
+MK_DEV unsigned cover_mask_of(const GridDesc& g, int gq)
+{
+    return g.cover_violated != nullptr ? ~mk_uniform(g.cover_violated[gq]) & 0xfffeu : 0u;
+}
+// The word a tile SORTS a record by: the record's 8 x 4-bit class ids with nibble 7 cleared where channel 7 carries a covered
+// class that one of channels 0..6 of the same record carries too -- that channel's group tests the atom with the same bits
+// (same LDS coordinates, same x-reach sub-bucket, same class => same `fast` choice and w) and its flush goes into channel 7's
+// accumulators as well (process_classes).  XOR with the broadcast nibble turns "equals nibble 7" into "is a zero nibble".
+MK_DEV unsigned cover_sort_ids(unsigned ids, unsigned cover)
+{
+    const unsigned n7 = ids >> 28;
+    const unsigned x = (ids ^ (n7 * 0x11111111u)) | 0xf0000000u;         // (nibble 7 itself must not count)
+    const bool dup = ((cover >> n7) & 1u) != 0u && ((x - 0x11111111u) & ~x & 0x88888888u) != 0u;   // exact "has a zero nibble"
+    return dup ? ids & 0x0fffffffu : ids;
+}
 // is item b of a batch-handle call (GridDesc::topo_offsets) the handle's item -- the same atoms of the resident batch?
 MK_DEV bool topo_batch_item_ok(const GridDesc& g, const long long* __restrict__ atom_offsets, int b)
 {
@@ -1108,14 +1130,18 @@ MK_KERNEL(256) void k_topology_classes(const SigT* __restrict__ sigmas, long lon
         block_sets[(size_t)blockIdx.x * CLS_BLOCK_SET + threadIdx.x] = s_full ? CLS_TOO_MANY : s_set[threadIdx.x];
 }
 
+// `violated` (optional, [G] words zeroed by the caller): the cover fold's input (GridDesc::cover_violated) -- bit s of word gq is
+// raised when an atom has class s in one of channels 0..6 of group gq and another class (or none) in the group's channel 7.
+// The bits of a wave meet in registers; one atomic per wave and group, and only from a wave that has a bit to add.
 template <typename SigT>
 MK_KERNEL(256) void k_topology_ids(const SigT* __restrict__ sigmas, const uint2* __restrict__ cw_in, const unsigned* __restrict__ cls_table,
                                    long long n, int C, int G, double w_scale, float w_exact_max,
                                    unsigned* __restrict__ ids_out /* [n, G] */, int* __restrict__ flags /* [0] |= 1: some sigma is wide; [1]: how many atoms */,
-                                   unsigned* __restrict__ wide_list /* [n]: the atoms with a wide sigma, in the order they arrive (the host sorts) */)
+                                   unsigned* __restrict__ wide_list /* [n]: the atoms with a wide sigma, in the order they arrive (the host sorts) */,
+                                   unsigned* __restrict__ violated = nullptr)
 {
     const long long a = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= n) return;
+    const bool act = a < n;                                          // (no early exit: the waves reduce the violated bits together)
     unsigned tab[NCLS];
 #pragma unroll
     for (int i = 0; i < NCLS; ++i) tab[i] = cls_table[i];
@@ -1127,18 +1153,32 @@ MK_KERNEL(256) void k_topology_ids(const SigT* __restrict__ sigmas, const uint2*
     };
     bool wide = false;
     for (int gq = 0; gq < G; ++gq) {
-        const uint2 cw = cw_in[(size_t)a * G + gq];
         unsigned ids = 0u;
-        if (cw.y != ATOM_MULTI_SIGMA) {
-            ids = class_of(cw.x) * cw.y;                             // ids <= 15: no carry between nibbles (fill_record's rule)
-            wide |= cw.x != CLS_EMPTY && mk_uint_as_float(cw.x) < w_exact_max;
-        } else {
-            float w[CHG];
-            atom_channel_w(sigmas + (size_t)a * C, gq * CHG, C, w_scale, w);
-            for (int c = 0; c < CHG; ++c)
-                if (w[c] < mk_inf()) { ids |= class_of(mk_float_bits(w[c])) << (4 * c); wide |= w[c] < w_exact_max; }
+        if (act) {
+            const uint2 cw = cw_in[(size_t)a * G + gq];
+            if (cw.y != ATOM_MULTI_SIGMA) {
+                ids = class_of(cw.x) * cw.y;                             // ids <= 15: no carry between nibbles (fill_record's rule)
+                wide |= cw.x != CLS_EMPTY && mk_uint_as_float(cw.x) < w_exact_max;
+            } else {
+                float w[CHG];
+                atom_channel_w(sigmas + (size_t)a * C, gq * CHG, C, w_scale, w);
+                for (int c = 0; c < CHG; ++c)
+                    if (w[c] < mk_inf()) { ids |= class_of(mk_float_bits(w[c])) << (4 * c); wide |= w[c] < w_exact_max; }
+            }
+            ids_out[(size_t)a * G + gq] = ids;
         }
-        ids_out[(size_t)a * G + gq] = ids;
+        if (violated != nullptr) {                                   // uniform
+            const unsigned n7 = ids >> 28;
+            unsigned v = 0u;
+#pragma unroll
+            for (int c = 0; c < CHG - 1; ++c) {
+                const unsigned id = (ids >> (4 * c)) & 0xfu;
+                v |= (id != 0u && id != n7) ? 1u << id : 0u;
+            }
+#pragma unroll
+            for (int d = 1; d < WAVE; d <<= 1) v |= mk_shfl(v, (int)((threadIdx.x & (WAVE - 1)) ^ (unsigned)d));
+            if ((threadIdx.x & (WAVE - 1)) == 0 && v != 0u) mk_atomic_or(reinterpret_cast<int*>(violated) + gq, (int)v);
+        }
     }
     if (wide) {
         mk_atomic_or(flags, 1);
@@ -1822,6 +1862,25 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
     const float4* __restrict__ w1p = rec_w + (size_t)(gq * 2 + 1) * g.M;
     // lane s < NCLS holds the w bits of class s (read back with a uniform-lane register read)
     const unsigned my_class_w = (lane < NCLS) ? table_word : INF_BITS;
+    // ---- cover fold (GridDesc::cover_violated; 0 = off) ----
+    // A class s is COVERED when every atom of the handle that has class s in a channel 0..6 of this group has it in channel 7
+    // too (the reference's `occupancies` channel: every heavy atom at the radius its other channels carry).  Such an atom would be
+    // put into LDS twice and tested against all 64 lanes x K planes twice, same arithmetic, same bits.  Here it is sorted without its
+    // channel-7 entry (cover_sort_ids, applied wherever a record's ids are counted or placed: histogram and placement agree by
+    // construction), and the flush of every group (c != 7, covered class) goes into q[7] as well.  Identity:
+    //   * per entry the two tests see the same bits: LDS coordinates, x-reach sub-bucket, `fast` (a function of the class's w), w;
+    //   * a minimum over a set is the minimum of the minima of its parts, m + c_k^2 is monotone in m (rounding is), and
+    //     f(d2) = d2 < R2 ? |d2| * w : INF is monotone for d2 >= 0, so min over the parts of f(min) == f(min over all);
+    //   * d2 < 0 happens in the fast form only, for an atom on a voxel centre: rounding leaves |d2| <= ~4e-6 (a few ulp of
+    //     c_max^2 = 12.25), and there |d2| is not monotone.  Folded and unfolded then both hold a value <= 4e-6 * w <= 4e-6 *
+    //     FAST_W_MAX < 3e-5 (the fold's minimum includes the unfolded one's term), and occupancy_from_q gives exactly 1.0f for every
+    //     q < 0.6 (x = q^-6 > 21, exp2(-1.44 x) < 2^-30 vanishes against 1): the stored float is the same.
+    // The DENSE instance stores every channel as it finishes: it keeps the full lists and folds nothing.
+    const unsigned cover = DENSE ? 0u : cover_mask_of(g, gq);
+    auto sort_ids = [&](unsigned ids) {
+        if (cover != 0u) { mk_stay_in_branch(); ids = cover_sort_ids(ids, cover); }      // wave-uniform
+        return ids;
+    };
 
     if (!general) {
         MK_PHASE_MARK(0);                                   // prologue
@@ -1844,6 +1903,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
         mk_block_sync();
         auto count_entry = [&](bool surv, unsigned, float ex, float ey, float ez, unsigned ids, int pk) {
             const int xr = x_reach(ex, ey, ez, pk);
+            ids = sort_ids(ids);
             for_each_present_channel(surv ? ids : 0u, [&](int c, unsigned id) {
                 (void)mk_lds_add(&bucket[(c * NSLOT + (int)id - 1) * NXR + xr], 1u);
             });
@@ -1851,6 +1911,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
         // A team's wave sees every TEAM-th batch of chunks; what survives the cull goes to the team's list (see above)
         auto count_and_list = [&](bool surv, unsigned, float ex, float ey, float ez, unsigned ids, int pk) {
             const int xr = x_reach(ex, ey, ez, pk);
+            ids = sort_ids(ids);                              // (the list keeps the word the tile sorts by)
             const unsigned long long m = mk_ballot(surv);
             unsigned base = 0u;
             if (lane == 0 && m != 0ull) base = mk_lds_add(&s_nsv, (unsigned)mk_popc64(m));
@@ -2071,7 +2132,15 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
 #pragma unroll
                 for (int k = 0; k < KL; ++k) {
                     const float d2 = fast ? m[k] + pl_x(k) * pl_x(k) : m[k];         // (plane_d2: g_k + c_k^2)
-                    acc[k] = mk_min_bits(acc[k], d2 < R2 ? mk_abs(d2) * wcls : INF);
+                    m[k] = d2 < R2 ? mk_abs(d2) * wcls : INF;
+                    acc[k] = mk_min_bits(acc[k], m[k]);
+                }
+                // cover fold: channel 7 left these atoms out of its own lists (a team's wave folds its own partial flush)
+                if constexpr (!DENSE) {
+                    if (c != CHG - 1 && ((cover >> (cls + 1)) & 1u) != 0u && !(MK_DIAG & (2 | 128))) {      // wave-uniform
+#pragma unroll
+                        for (int k = 0; k < KL; ++k) q[CHG - 1][k] = mk_min_bits(q[CHG - 1][k], m[k]);
+                    }
                 }
             }
         };
@@ -2107,7 +2176,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
                 });
             };
             auto place_entry = [&](bool surv, unsigned, float ex, float ey, float ez, unsigned ids, int pk) {
-                place_at(surv, ex, ey, ez, ids, x_reach(ex, ey, ez, pk));
+                place_at(surv, ex, ey, ez, sort_ids(ids), x_reach(ex, ey, ez, pk));
             };
             if (MK_DIAG & 64) {
             } else if (use_list) {

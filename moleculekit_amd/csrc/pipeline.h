@@ -75,6 +75,11 @@ struct TopologyDev {
     const long long* h_offsets = nullptr;   // the same on the host (a call's range: its first atom, its atom count)
     const unsigned* h_wide_list = nullptr;  // wide_list on the host (the wide atoms inside a call's range)
     long long max_item = 0;                 // atoms of the longest item (k_exact_redo's slices)
+    // cover fold (round 8): the build's violated-class words, [G] on the device (GridDesc::cover_violated; nullptr: a handle built
+    // without them -- no fold), and what the host keeps of them: cover[g] = ~violated[g] & 0xfffe, the classes channel 7 of group g
+    // covers.  A property of the handle's atoms, so it holds for any item range of a batch handle.
+    const unsigned* cover_violated = nullptr;
+    const unsigned* h_cover = nullptr;
 };
 
 struct LatticeProblem {
@@ -98,6 +103,7 @@ struct LatticeProblem {
     unsigned seq = 0;                       // != 0: k_tail reports this number in the host-visible feedback words as it starts (FB_TILES_DONE)
     int tile_team = -1;                     // -1 = automatic (a team of waves per tile when the launch is tiny), 0 = never, 1 = always (4, 8, 16: with that many waves)
     int tile_items = -1;                    // -1 = automatic (a workgroup per item for batches of ligand-sized items), 0 = never, 1 = always
+    int cover_fold = 0;                     // 0 = a call that bins through a handle folds covered channels (GridDesc::cover_violated), -1 = never (A-B, tests)
     int exact_redo_list = 0;                // 0 = a topology call with wide atoms hands its exact cut-off hits to k_exact_redo, -1 = k_tail recomputes them in place;
                                             // n > 0 (tests): as 0 with a list of n hits
     // device pointers
@@ -713,6 +719,8 @@ int run_lattice(BE& be, const LatticeProblem& P_in, std::string& err)
     const int tier = choose_tier(P.lds_tier, be.feedback_host());
     // a topology call: the tile kernels read the handle's table (nobody writes through it: k_tail's table is a solo call's)
     if (L.topo()) W.cls_table = const_cast<unsigned*>(P.topo->table);
+    // ... and, binning through the handle, leave the atoms channel 7 covers out of its lists (every other route: the full lists)
+    g.cover_violated = L.topo() && P.cover_fold >= 0 ? P.topo->cover_violated : nullptr;
     if (L.split_exact_fixup) {
         if ((st = ensure_as(be, WS_REDO_LIST, (size_t)(REDO_HEAD + (size_t)REDO_CAP * REDO_ENTRY) * sizeof(unsigned), W.redo_list, set))) return st;
         // (the list's counter back to zero: queued behind the previous call's k_exact_redo on this stream, in front of this call's hot kernels)
@@ -742,7 +750,8 @@ int run_lattice(BE& be, const LatticeProblem& P_in, std::string& err)
 // flags[0] back once the stream has drained.  Workspace: the class-set slots of set 0.
 template <class BE>
 int run_topology_build(BE& be, const void* d_sigmas, int sigmas_f64, long long n, int C, double voxelsize, uint2* cw, unsigned* ids,
-                       unsigned* table, int* flags /* 2 words, zeroed */, unsigned* wide_list /* [n] */, std::string& err)
+                       unsigned* table, int* flags /* 2 words, zeroed */, unsigned* wide_list /* [n] */, std::string& err,
+                       unsigned* violated = nullptr /* [G] words, zeroed: the cover fold's input (TopologyDev::cover_violated) */)
 {
     if (n <= 0 || C <= 0) { err = "a topology needs n_atoms > 0 and n_channels > 0"; return ST_EINVAL; }
     if (!(voxelsize > 0.0) || !std::isfinite(voxelsize)) { err = "voxelsize must be a positive finite number"; return ST_EINVAL; }
@@ -760,7 +769,7 @@ int run_topology_build(BE& be, const void* d_sigmas, int sigmas_f64, long long n
         if ((s = be.launch(k_topology_classes<S>, dim3(nblk), dim3(256), sig, n, C, G, w_scale, cw, bsets))) return s;
         if ((s = be.launch(k_merge_classes, dim3(nl1), dim3(256), bsets, nblk, (unsigned)CLS_BLOCK_SET, CLS_ROWS_PER_BLOCK, l1sets, (unsigned*)nullptr))) return s;
         if ((s = be.launch(k_merge_classes, dim3(1), dim3(256), l1sets, nl1, (unsigned)MERGE_SET, nl1, (unsigned*)nullptr, table))) return s;
-        return be.launch(k_topology_ids<S>, dim3(nblk), dim3(256), sig, cw, table, n, C, G, w_scale, w_exact_max, ids, flags, wide_list);
+        return be.launch(k_topology_ids<S>, dim3(nblk), dim3(256), sig, cw, table, n, C, G, w_scale, w_exact_max, ids, flags, wide_list, violated);
     });
 }
 

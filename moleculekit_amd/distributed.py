@@ -197,6 +197,8 @@ class ShardedVoxelizer:
         if self._shared:
             from . import _lib
             tctx = self._ctx or _lib.default_context(self.device.index if self.device.index is not None else 0)
+            if os.environ.get("MKAMD_COVER_FOLD", "1") == "0":       # (A-B of one build: every channel keeps its full lists)
+                tctx.set_cover_fold(-1)
             if not getattr(tctx, "_force_general", False) and not getattr(tctx, "_value_tol", 0.0):
                 torch.cuda.current_stream(self.device).synchronize()
                 try:
@@ -213,12 +215,15 @@ class ShardedVoxelizer:
             # (3c)); coordinates, origins and affines may change from call to call, the sigmas do not.  Kept only where the library says
             # the shard's calls would use it (ligand-sized items and one-molecule calls take other pre-passes), never for the A-B modes
             # of a context; more than 15 distinct sigmas: the plain call.  MKAMD_BATCH_TOPOLOGY=0 (read here, once): the plain call.
+            # MKAMD_COVER_FOLD=0 (read here as well): the handle's calls keep every channel's full lists (Context.set_cover_fold(-1)).
             # self._d["sigmas"] stays resident either way (other callers slice it).
             # Items that all repeat ONE sigma matrix are frames of one molecule: `shared_sigmas` is the handle for those (one copy of the
             # matrix), and a caller who leaves it off there asks for the plain call -- the cross-check of the frame handle, the
             # benchmark's plain leg of its trajectory workloads -- and gets it.
             from . import _lib
             tctx = self._ctx or _lib.default_context(self.device.index if self.device.index is not None else 0)
+            if os.environ.get("MKAMD_COVER_FOLD", "1") == "0":
+                tctx.set_cover_fold(-1)
             if not getattr(tctx, "_force_general", False) and not getattr(tctx, "_value_tol", 0.0):
                 torch.cuda.current_stream(self.device).synchronize()
                 try:
