@@ -4,6 +4,7 @@
 #include "align_kernels.h"
 #include "pipeline.h"
 
+#include <cstdio>
 #include <string>
 
 namespace mkamd {
@@ -36,6 +37,24 @@ inline AlignPlan align_plan(long long n, long long n_items, int cus)
     p.seg_len = (int)seg_len;
     p.blocks_x = (unsigned)((n_items + (AL_BLOCK / G) - 1) / (AL_BLOCK / G));
     return p;
+}
+
+// What a call launched for its frames, for mkamd_ctx_last_dist_kernel: the k_align_sums instantiation, the lane-group width, and the
+// fold exactly when the frames' records were cut into segments (the reference's own pass of AL_SINGLE is not named).  A backend that
+// keeps no note (it has no note_dist_kernel) runs the same plans without one.
+template <class BE>
+auto align_note_to(BE& be, const char* name, int) -> decltype(be.note_dist_kernel(name), void()) { be.note_dist_kernel(name); }
+template <class BE>
+void align_note_to(BE&, const char*, long) {}
+
+template <class BE>
+void align_note(BE& be, const char* mode, const AlignPlan& p, const char* fold)
+{
+    static_assert(AL_SHP == 17 && AL_NS == 24, "the fold's name below spells these out");
+    char name[96];
+    snprintf(name, sizeof name, "mkamd::k_align_sums<%s> G=%d segs=%d%s%s", mode, 1 << p.glog2, p.segs, p.segs > 1 ? " + mkamd::" : "",
+             p.segs > 1 ? fold : "");
+    align_note_to(be, name, 0);
 }
 
 struct AlignArgs {
@@ -91,6 +110,7 @@ int run_align_transforms(BE& be, const AlignArgs& a, double* affine, double* fit
         }
     }
     const AlignPlan p = align_plan(a.n, a.n_list, be.compute_units());
+    align_note(be, a.matching ? "AL_MATCH" : "AL_SINGLE", p, "k_align_fold<17, 24>");
     void* w = nullptr;
     if ((st = be.ensure(WS_A_PART, (size_t)a.n_list * p.segs * AL_NS * sizeof(double), &w, 0))) return st;
     const dim3 grid(p.blocks_x, (unsigned)p.segs);
@@ -138,6 +158,7 @@ int run_align_rmsd(BE& be, const AlignArgs& a, const double* affine, float* rmsd
     if (!affine) { err = "NULL affine"; return ST_EINVAL; }
     int st;
     const AlignPlan p = align_plan(a.n, a.n_list, be.compute_units());
+    align_note(be, "AL_RMSD", p, "k_align_fold<1, 1>");
     void* w = nullptr;
     if ((st = be.ensure(WS_A_RPART, (size_t)a.n_list * p.segs * sizeof(double), &w, 0))) return st;
     if ((st = be.launch(k_align_sums<AL_RMSD>, dim3(p.blocks_x, (unsigned)p.segs), dim3(AL_BLOCK), a.xyz, 3 * a.n_atoms, a.ref,

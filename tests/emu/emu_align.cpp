@@ -18,6 +18,8 @@ struct AlignEmuBackend {
     size_t caps[WS_NSLOTS] = {};
     int compute_units() const { return cus; }
     int cus = 256;
+    std::string kernel;
+    void note_dist_kernel(const char* name) { kernel = name; }
     ~AlignEmuBackend() { for (void* p : bufs) free(p); }
     int ensure(int slot, size_t bytes, void** ptr, int = 0)
     {
@@ -39,7 +41,7 @@ struct AlignEmuBackend {
     }
 };
 
-thread_local std::string g_err;
+thread_local std::string g_err, g_kernel;
 
 AlignArgs args(const float* xyz, long long N, long long F, const float* ref, long long Nr, long long Fr, const unsigned* sel,
                const unsigned* refsel, long long n, const long long* frames, long long K, long long refframe, int matching)
@@ -59,6 +61,9 @@ extern "C" {
 
 const char* emu_align_last_error() { return g_err.c_str(); }
 
+// run_align_transforms' / run_align_rmsd's note of the last call (what mkamd_ctx_last_dist_kernel reports on the device)
+const char* emu_align_last_kernel() { return g_kernel.c_str(); }
+
 // cus: the compute-unit count the launch plan assumes (segments of the selection: few frames are split over many waves)
 int emu_align_transforms(int cus, const float* xyz, long long N, long long F, const float* ref, long long Nr, long long Fr,
                          const unsigned* sel, const unsigned* refsel, long long n, const long long* frames, long long K,
@@ -67,7 +72,9 @@ int emu_align_transforms(int cus, const float* xyz, long long N, long long F, co
     AlignEmuBackend be;
     be.cus = cus;
     g_err.clear();
-    return run_align_transforms(be, args(xyz, N, F, ref, Nr, Fr, sel, refsel, n, frames, K, refframe, matching), affine, fit_rmsd, g_err);
+    const int st = run_align_transforms(be, args(xyz, N, F, ref, Nr, Fr, sel, refsel, n, frames, K, refframe, matching), affine, fit_rmsd, g_err);
+    g_kernel = be.kernel;
+    return st;
 }
 
 int emu_align_apply(const float* xyz, long long N, const long long* frames, long long K, const double* affine, float* out)
@@ -84,7 +91,9 @@ int emu_align_rmsd(int cus, const float* xyz, long long N, long long F, const fl
     AlignEmuBackend be;
     be.cus = cus;
     g_err.clear();
-    return run_align_rmsd(be, args(xyz, N, F, ref, Nr, Fr, sel, refsel, n, frames, K, refframe, matching), affine, rmsd, g_err);
+    const int st = run_align_rmsd(be, args(xyz, N, F, ref, Nr, Fr, sel, refsel, n, frames, K, refframe, matching), affine, rmsd, g_err);
+    g_kernel = be.kernel;
+    return st;
 }
 
 int emu_align_plan(long long n, long long n_items, int cus, int* out4)

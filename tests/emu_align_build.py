@@ -40,6 +40,7 @@ def lib():
         build()
         L = ctypes.CDLL(_LIB)
         L.emu_align_last_error.restype = ctypes.c_char_p
+        L.emu_align_last_kernel.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -67,6 +68,7 @@ def _inputs(xyz, ref, sel, refsel, frames):
 def transforms(xyz, ref, sel, refsel, frames=None, refframe=0, matching=False, cus=256):
     """xyz float32 [F,N,3], ref [Fr,Nr,3] (or [Nr,3]) -> (affine float64 [K,12], fit_rmsd float64 [K])"""
     xyz, ref, sel, refsel, fr = _inputs(xyz, ref, sel, refsel, frames)
+    cus = 256 if cus is None else cus
     K = xyz.shape[0] if fr is None else len(fr)
     aff = np.full((K, 12), np.nan)
     rms = np.full(K, np.nan)
@@ -96,6 +98,22 @@ def apply_raw(xyz_flat, n_atoms, affine, frames, out_flat):
                                  _p(np.ascontiguousarray(affine, np.float64)), _p(out_flat)))
 
 
+def apply_at(base, off_in, outbuf, off_out, n_atoms, n_frames, affine, frames):
+    """tests/align_cases.py's driver call: the frames at base[off_in:] moved to outbuf[off_out:] (outbuf None: in place); returns the
+    whole output buffer"""
+    n = 3 * n_atoms * n_frames
+    if outbuf is None:
+        outbuf = base
+    apply_raw(base[off_in:off_in + n], n_atoms, affine, frames, outbuf[off_out:off_out + n])
+    return outbuf
+
+
+def rmsd_trajectory(xyz, ref, alnsel, rmsdsel, frames=None):
+    """align.rmsd_trajectory's sequence: the transforms over alnsel, then the RMSD over rmsdsel"""
+    aff, _ = transforms(xyz, ref, alnsel, alnsel, frames=frames)
+    return rmsd(xyz, ref, rmsdsel, rmsdsel, aff, frames=frames)
+
+
 def rmsd(xyz, ref, sel, refsel, affine, frames=None, refframe=0, matching=False, cus=256):
     xyz, ref, sel, refsel, fr = _inputs(xyz, ref, sel, refsel, frames)
     K = xyz.shape[0] if fr is None else len(fr)
@@ -105,6 +123,11 @@ def rmsd(xyz, ref, sel, refsel, affine, frames=None, refframe=0, matching=False,
                                 ctypes.c_longlong(len(sel)), _p(fr), ctypes.c_longlong(K), ctypes.c_longlong(refframe),
                                 ctypes.c_int(int(bool(matching))), _p(np.ascontiguousarray(affine, np.float64)), _p(out)))
     return out
+
+
+def last_kernel():
+    """The note of the last transforms / rmsd call (run_align_transforms / run_align_rmsd: ctx.last_dist_kernel() on the device)."""
+    return lib().emu_align_last_kernel().decode()
 
 
 def plan(n, n_items, cus=256):

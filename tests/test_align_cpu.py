@@ -1,11 +1,15 @@
 """CPU tier of the alignment row (moleculekit_amd/align.py, csrc/align_kernels.h): the kernels through the host SIMT emulation
-(tests/emu_align_build.py) against a float64 Kabsch restatement written here, and the host logic of the drop-in."""
+(tests/emu_align_build.py) against the float64 Kabsch restatement of tests/align_cases.py, the cases the GPU tier runs on the hardware
+(tests/align_cases.py: the same inputs under the same conditions), and the host logic of the drop-in."""
 import os
 import sys
 import types
 
 import numpy as np
 import pytest
+
+from tests import align_cases as C
+from tests.align_cases import apply64, fit_rmsd64, kabsch64, np_pp_align, rot, traj, within_ulp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "align_cases.npz")
@@ -16,53 +20,6 @@ def E():
     from tests import emu_align_build
     emu_align_build.build()
     return emu_align_build
-
-
-def kabsch64(P, Q):
-    """float64 Kabsch (SVD with the reflection sign): R, t with R P_i + t ~ Q_i"""
-    P = np.asarray(P, np.float64)
-    Q = np.asarray(Q, np.float64)
-    cP, cQ = P.mean(0), Q.mean(0)
-    H = (P - cP).T @ (Q - cQ)
-    V, S, Wt = np.linalg.svd(H)
-    W = Wt.T
-    Z = np.eye(3)
-    Z[2, 2] = np.sign(np.linalg.det(W) * np.linalg.det(V))
-    R = W @ Z @ V.T
-    return R, cQ - R @ cP
-
-
-def apply64(x, R, t):
-    return (np.asarray(x, np.float64) @ R.T + t).astype(np.float32)
-
-
-def fit_rmsd64(P, Q, R, t):
-    d = apply64_d(P, R, t) - np.asarray(Q, np.float64)
-    return np.sqrt((d * d).sum() / len(P))
-
-
-def apply64_d(x, R, t):
-    return np.asarray(x, np.float64) @ R.T + t
-
-
-def rot(rng):
-    q = rng.normal(size=4)
-    q /= np.linalg.norm(q)
-    w, x, y, z = q
-    return np.array([[w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z]])
-
-
-def traj(rng, N, F, noise=0.3, spread=10.0):
-    ref = (rng.normal(size=(N, 3)) * spread).astype(np.float32)
-    xyz = np.stack([(ref @ rot(rng).T + rng.uniform(-1000, 1000, 3) + rng.normal(scale=noise, size=(N, 3))).astype(np.float32)
-                    for _ in range(F)])
-    return xyz, ref
-
-
-def within_ulp(got, exp, ulps=1):
-    return np.all(np.abs(got.astype(np.float64) - exp.astype(np.float64)) <= ulps * np.spacing(np.abs(exp)).astype(np.float64))
 
 
 @pytest.mark.parametrize("N,nsel,F", [(7, 7, 5), (50, 23, 9), (301, 300, 3), (1000, 1, 2), (5000, 5000, 1), (130, 64, 17)])
@@ -117,39 +74,15 @@ def test_reflected_copy_gives_proper_rotation(E):
 
 @pytest.mark.parametrize("kind", ["coplanar", "collinear"])
 def test_degenerate_selections(E, kind):
-    """the rotation is not unique: checked by the fit RMSD and the selection's residual only"""
-    rng = np.random.default_rng(5)
-    P = rng.normal(scale=5, size=(20, 3))
-    P[:, 2] = 0.0
-    if kind == "collinear":
-        P[:, 1] = 0.0
-    P = P.astype(np.float32)
-    Rt = rot(rng)
-    xyz = (P @ Rt.T + 50.0).astype(np.float32)[None]
-    aff, fit = E.transforms(xyz, P, np.arange(20), np.arange(20))
-    R = aff[0, :9].reshape(3, 3)
-    assert abs(np.linalg.det(R) - 1.0) < 1e-12 and np.abs(R @ R.T - np.eye(3)).max() < 1e-12
-    out = E.apply(xyz, aff)
-    assert np.abs(out[0] - P).max() < 1e-3
-    assert fit[0] < 1e-5
+    C.check_degenerate(E, kind)
 
 
 def test_one_atom_and_zero_covariance_give_identity(E):
-    xyz = np.zeros((2, 5, 3), np.float32)
-    xyz[1] += 3.0
-    ref = np.ones((5, 3), np.float32)
-    aff, fit = E.transforms(xyz, ref, np.arange(5), np.arange(5))   # all atoms coincident
-    for f in range(2):
-        assert np.array_equal(aff[f, :9], np.eye(3).ravel())
-    out = E.apply(xyz, aff)
-    assert np.array_equal(out, np.ones_like(xyz))
+    C.check_coincident(E)
 
 
 def test_empty_selection_gives_nan(E):
-    xyz, ref = traj(np.random.default_rng(1), 10, 2)
-    aff, fit = E.transforms(xyz, ref, np.zeros(0, np.uint32), np.zeros(0, np.uint32))
-    assert np.all(np.isnan(aff[:, 9:])) and np.all(np.isnan(fit))
-    assert np.all(np.isnan(E.apply(xyz, aff)))
+    C.check_empty(E)
 
 
 def test_matching_frames_and_frame_lists(E):
@@ -225,18 +158,49 @@ def test_runs_are_bitwise_equal(E):
     assert np.array_equal(E.apply(xyz, a1), E.apply(xyz, a2))
 
 
+# ---- the cases of tests/align_cases.py: what the GPU tier runs on the hardware, here on the emulation ------------------------------
+@pytest.mark.parametrize("F", C.WIDTH_FRAMES)
+@pytest.mark.parametrize("n", C.WIDTH_SIZES)
+def test_group_widths_and_partial_waves(E, n, F):
+    for matching in (False, True):
+        for listed in (False, True):
+            C.check_width(E, n, F, matching, listed)
+
+
+def test_matching_frames_segmented(E):
+    C.check_segmented_match(E)
+
+
+def test_unsegmented_long_walk_and_its_segmented_twin(E):
+    """(the 4 096 frames that make the device's plan walk 300 atoms with one lane group run in the GPU tier only; here 8 frames on a plan
+    for one compute unit take the same form)"""
+    assert E.plan(300, 8, cus=1)["segs"] == 1 and E.plan(300, 4096)["segs"] == 1 and E.plan(300, 3)["segs"] > 1
+    C.check_two_plans(E, 8, 1, cus=1)
+
+
+@pytest.mark.parametrize("N", C.APPLY_SIZES)
+def test_apply_every_placement_gives_the_same_bits(E, N):
+    C.check_apply_alignment(E, N)
+
+
+def test_rmsd_over_another_selection(E):
+    C.check_rmsd(E)
+
+
+@pytest.mark.parametrize("matching", [False, True])
+def test_route_case_matches_the_restatement(E, matching):
+    """the data the GPU tier hands to _pp_align and to align_trajectory (equal bits there), here against the float64 restatement in the
+    reference's layout"""
+    c = C.route_case()
+    for frames in C.ROUTE_FRAMES:
+        fr = None if frames is None else np.array(frames)
+        aff, _ = E.transforms(c.xyz, c.refs_fm if matching else c.ref_fm, c.sel, c.sel, frames=fr, matching=matching)
+        got = E.apply(c.xyz, aff, frames=fr).transpose(1, 2, 0)
+        exp = np_pp_align(c.coords, c.refs if matching else c.ref, c.sel, c.sel, range(c.F) if frames is None else frames, 0, matching)
+        assert within_ulp(got, exp)
+
+
 # ---- the fixture ------------------------------------------------------------------------------------------------------
-def np_pp_align(coords, refcoords, sel, refsel, frames, refframe, matching):
-    """the float64 restatement in the reference's layout (snapshot of the reference frame)"""
-    out = coords.copy()
-    ref = refcoords.copy()
-    for f in frames:
-        Q = ref[refsel, :, f] if matching else ref[refsel, :, refframe]
-        R, t = kabsch64(coords[sel, :, f], Q)
-        out[:, :, f] = apply64(coords[:, :, f], R, t)
-    return out
-
-
 @pytest.mark.parametrize("case", ["selfalign", "refmol", "matching", "selected"])
 def test_restatement_reproduces_reference_held_arrays(case):
     g = np.load(GOLDEN)

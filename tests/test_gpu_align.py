@@ -1,11 +1,13 @@
 """GPU tier of the alignment row (moleculekit_amd/align.py): the reference's own alignment and MetricRmsd answers on its trajectory
-(tests/golden/align_cases.npz, tests/golden/make_golden_align.py), a large trajectory against a float64 restatement, and the
-aligned voxel streams against aligned-then-voxelized frames."""
+(tests/golden/align_cases.npz, tests/golden/make_golden_align.py), a large trajectory against a float64 restatement, the
+aligned voxel streams against aligned-then-voxelized frames, and every launch plan and apply path of the kernels on the cases of
+tests/align_cases.py (shared with the emulator tier), the plan taken asserted through ``ctx.last_dist_kernel()``."""
 import os
 
 import numpy as np
 import pytest
 
+from tests import align_cases as C
 from tests.cases import TOL
 
 pytestmark = pytest.mark.gpu
@@ -220,3 +222,125 @@ def test_aligned_xtc_stream_with_getchannels_shaped_sigmas(hip_ctx, ions):
     worst = max(float(np.abs(streamed[f].cpu().numpy() - oracle.calculate_occupancy(centers, a[f], sig)).max()) for f in (0, 17, 39))
     print(f"aligned stream, getChannels-shaped sigmas, {ions} ions: {worst:.2e}")
     assert worst <= TOL
+
+
+# ------------------------------------------------------------------------------------------------
+# every launch plan and apply path on the hardware: the cases of tests/align_cases.py, which tests/test_align_cpu.py runs on the
+# emulation -- the same inputs under the same conditions, the plan asserted through ctx.last_dist_kernel()
+# ------------------------------------------------------------------------------------------------
+class Hardware:
+    """the driver of tests/align_cases.py on the device: numpy in, numpy out.  Every transforms and RMSD call is made twice and must
+    give the same bits both times."""
+
+    def __init__(self, ctx):
+        import torch
+        from moleculekit_amd import align
+        self.torch, self.align, self.ctx = torch, align, ctx
+        self.dev = torch.device("cuda", ctx.device)
+
+    def up(self, a):
+        return self.torch.as_tensor(np.array(a), device=self.dev)            # (a copy: the shared cases are read-only arrays)
+
+    @staticmethod
+    def same_bits(a, b):
+        return a.dtype == b.dtype and a.shape == b.shape and bool((a.view(np.int64 if a.itemsize == 8 else np.int32)
+                                                                   == b.view(np.int64 if b.itemsize == 8 else np.int32)).all())
+
+    def transforms(self, xyz, ref, sel, refsel, frames=None, refframe=0, matching=False, cus=None):
+        A = self.align
+        d_xyz, d_ref = A._xyz3("xyz", self.up(xyz)), A._xyz3("ref", self.up(ref))
+        ctx, dev = A._torch_ctx(d_xyz, self.ctx)
+        d_sel, d_refsel = A._dev_sel(np.asarray(sel), d_xyz.shape[1], "sel", dev), A._dev_sel(np.asarray(refsel), d_ref.shape[1], "refsel", dev)
+        d_fr, K = A._dev_frames(frames, int(d_xyz.shape[0]), dev)
+        runs = []
+        for _ in range(2):                                                     # float64 fit RMSD: what the kernel writes, not its float32 copy
+            aff, fit = A._transforms(ctx, dev, d_xyz, d_ref, d_sel, d_refsel, d_sel.numel(), d_fr, K, refframe, matching)
+            runs.append((aff.cpu().numpy(), fit.cpu().numpy()))
+        assert self.same_bits(runs[0][0], runs[1][0]) and self.same_bits(runs[0][1], runs[1][1]), "two runs of the transforms differ"
+        return runs[0]
+
+    def apply(self, xyz, affine, frames=None):
+        return self.align.apply_transforms(self.up(xyz), self.up(affine), frames=frames, ctx=self.ctx).cpu().numpy()
+
+    def apply_at(self, base, off_in, outbuf, off_out, N, F, affine, frames):
+        n = 3 * N * F
+        d_base = self.up(base)
+        d_out = d_base if outbuf is None else self.up(outbuf)
+        src = d_base[off_in:off_in + n].view(F, N, 3)
+        dst = d_out[off_out:off_out + n].view(F, N, 3)
+        assert src.data_ptr() == d_base.data_ptr() + 4 * off_in and dst.data_ptr() == d_out.data_ptr() + 4 * off_out and d_base.data_ptr() % 16 == 0
+        assert d_out.data_ptr() % 16 == 0
+        got = self.align.apply_transforms(src, self.up(affine), frames=frames, out=dst, ctx=self.ctx)
+        assert got.data_ptr() == dst.data_ptr()
+        return d_out.cpu().numpy()
+
+    def rmsd_trajectory(self, xyz, ref, alnsel, rmsdsel, frames=None):
+        d_xyz, d_ref = self.up(xyz), self.up(ref)
+        a = self.align.rmsd_trajectory(d_xyz, d_ref, alnsel, alnsel, rmsdsel, rmsdsel, frames=frames, ctx=self.ctx).cpu().numpy()
+        b = self.align.rmsd_trajectory(d_xyz, d_ref, alnsel, alnsel, rmsdsel, rmsdsel, frames=frames, ctx=self.ctx).cpu().numpy()
+        assert self.same_bits(a, b), "two runs of the RMSD differ"
+        return a
+
+    def last_kernel(self):
+        return self.ctx.last_dist_kernel()
+
+
+@pytest.fixture(scope="module")
+def hw(hip_ctx):
+    return Hardware(hip_ctx)
+
+
+@pytest.mark.parametrize("F", C.WIDTH_FRAMES)
+@pytest.mark.parametrize("n", C.WIDTH_SIZES)
+def test_group_widths_and_partial_waves(hw, n, F):
+    """G = 8 / 16 / 32 / 64 by the selection's size, below, at and above every width; 13 and 37 frames leave waves and blocks partly
+    filled; one reference frame and matching frames, all frames and a list out of order"""
+    for matching in (False, True):
+        for listed in (False, True):
+            C.check_width(hw, n, F, matching, listed)
+
+
+def test_matching_frames_segmented(hw):
+    C.check_segmented_match(hw)
+
+
+def test_unsegmented_long_walk_and_its_segmented_twin(hw):
+    cus = hw.ctx.device_info()["compute_units"]
+    if 8 * cus > C.LONG_WALK["F"]:
+        pytest.skip(f"{cus} compute units: the plan cuts a 300-atom selection into segments even on {C.LONG_WALK['F']} frames")
+    C.check_two_plans(hw, C.LONG_WALK["F"], C.LONG_WALK["every"])
+
+
+@pytest.mark.parametrize("N", C.APPLY_SIZES)
+def test_apply_every_placement_gives_the_same_bits(hw, N):
+    C.check_apply_alignment(hw, N)
+
+
+def test_rmsd_over_another_selection(hw):
+    C.check_rmsd(hw)
+
+
+@pytest.mark.parametrize("matching", [False, True])
+def test_host_route_equals_tensor_route(hw, matching):
+    """_pp_align (host arrays in the reference's layout: mkamd_align_host) against align_trajectory on the transposed tensor"""
+    c = C.route_case()
+    for frames in C.ROUTE_FRAMES:
+        fr = np.arange(c.F) if frames is None else np.array(frames)
+        host = hw.align._pp_align(c.coords, c.refs if matching else c.ref, c.sel, c.sel, fr, 0, matching, inplace=False, ctx=hw.ctx)
+        dev = hw.align.align_trajectory(hw.up(c.xyz), hw.up(c.refs_fm if matching else c.ref_fm), c.sel, frames=fr, matchingframes=matching,
+                                        ctx=hw.ctx).cpu().numpy()
+        assert host.dtype == np.float32 and np.array_equal(C.bits(host), C.bits(dev.transpose(1, 2, 0))), (matching, frames)
+        assert not np.array_equal(host[:, :, fr], c.coords[:, :, fr])                      # (the alignment did something)
+
+
+@pytest.mark.parametrize("kind", ["coplanar", "collinear"])
+def test_degenerate_selections(hw, kind):
+    C.check_degenerate(hw, kind)
+
+
+def test_zero_covariance_gives_identity(hw):
+    C.check_coincident(hw)
+
+
+def test_empty_selection_gives_nan(hw):
+    C.check_empty(hw)
