@@ -646,7 +646,9 @@ def iterVoxelizeXTC(filename, channels, center, boxsize, voxelsize=1, pbc=True, 
                   no coordinate or run of small atoms packed into more than 64 bits, < 2^21 atoms), the host otherwise (a sparse selection would
                   copy the whole span of the file between its first and last frame).
     A frame the device decoder refuses after all, or a corrupt one, raises -- at the latest when the generator ends (like the
-    voxelizer's own asynchronous errors).
+    voxelizer's own asynchronous errors) -- and the features of its chunk are never yielded: the device path hands a chunk out
+    once its decode statuses were read, without waiting for them, so chunk k may arrive when up to three later ones are enqueued --
+    up to four chunks of features are then alive at a time (each ``chunk * V * C`` floats), not one: size ``chunk`` for that.
 
     ``align = (ref_xyz [n, 3] Angstrom, sel)``: as ``iterVoxelizeTrajectory``'s (needs ``pbc=False``)."""
     import ctypes
@@ -734,20 +736,22 @@ def _iter_xtc_gpu(filename, path, natoms, fr, box_lengths, nvoxels, has_box, cha
         h2d = torch.cuda.Stream(device=dev)                      #  in order on one stream: one work buffer)
         up = [torch.cuda.Event(), torch.cuda.Event()]            # the upload out of h_raw[slot] is done
         done = [torch.cuda.Event() for _ in range(NS)]           # chunk k's decode and status copy are done (k % NS)
-    in_flight = [None] * NS                                       # frame indices whose statuses h_st[k % NS] will hold
+    in_flight = [None] * NS                                       # (chunk, frame indices) whose statuses h_st[chunk % NS] will hold
+    cleared = set()                                               # chunks whose statuses were read and are all 0, features not yet yielded
 
     def check(ss, block):
-        idx = in_flight[ss]
-        if idx is None or not (block or done[ss].query()):
+        if in_flight[ss] is None or not (block or done[ss].query()):
             return
         if block:
             done[ss].synchronize()
+        k, idx = in_flight[ss]
         in_flight[ss] = None
         st = h_st[ss][:len(idx)].numpy()
         if st.any():
             bad = int(np.flatnonzero(st)[0])
             raise RuntimeError(f"{filename}: frame {int(idx[bad])} " + ("is corrupt" if st[bad] == 1 else "is outside what the device "
                                'decoder takes (a number of more than 64 bits): read this file with decode="host"'))
+        cleared.add(k)
 
     def fill_dev(copy, xyz, bx, idx):
         k = state["k"]
@@ -790,19 +794,29 @@ def _iter_xtc_gpu(filename, path, natoms, fr, box_lengths, nvoxels, has_box, cha
                                              natoms, 10.0, xyz.data_ptr(), d_st[slot].data_ptr(), work.data_ptr(), work.numel()))
         h_st[ss][:n].copy_(d_st[slot][:n], non_blocking=True)
         done[ss].record(copy)
-        in_flight[ss] = np.array(idx, copy=True)
+        in_flight[ss] = (k, np.array(idx, copy=True))
         return images
 
     gen = _stream_voxelize(natoms, fr, None, 10.0, has_box, channels, center, boxsize, voxelsize, chunk, device, channel_first,
                            run_ctx, max_images, fill_dev=fill_dev, pipelined=pipelined, ramp=ramp, align=align)
+    # A chunk's features are handed out only once ITS statuses were read and are all 0: a refused frame's items are whatever the slot held
+    # before.  Nothing waits for that -- a chunk is held back until its decode is seen done (at the latest when fill_dev needs its status
+    # buffer, NS chunks on, or at the end), so up to NS chunks of features are alive at a time.
+    held = []
     try:
-        for item in gen:
+        for k, item in enumerate(gen):
+            held.append((k, item))
             for ss in range(NS):
                 check(ss, False)
-            yield item
+            while held and held[0][0] in cleared:
+                cleared.discard(held[0][0])
+                yield held.pop(0)[1]
         for ss in range(NS):
             check(ss, True)
+        while held:
+            yield held.pop(0)[1]
     finally:
+        held.clear()
         gen.close()                                               # (synchronizes the copy stream, which waited for the uploads)
         h2d.synchronize()
         for i in range(2):

@@ -47,7 +47,10 @@ MK_DEV_CONST int XTC_MAGIC[73] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 8, 10, 12, 16, 20, 
 constexpr int XTC_FIRST = 9, XTC_NMAGIC = 73;
 
 constexpr int XTC_PAD = 1024;            // bytes the caller's byte buffer extends past the last record (windows and refills read
-                                         // ahead of what they use)
+                                         // ahead of what they use: a live lane's position is at most the end of its stream, and a
+                                         // refill reads XS_WIN bytes from the word it is in).  The whole pad is needed -- and nothing
+                                         // beyond it is read, on damaged streams either: tests/emu/xtc_damage_main.cpp runs both
+                                         // kernels under AddressSanitizer on buffers of exactly this size (tests/test_xtc_damage.py)
 
 struct XtcBits {                         // MSB-first bit reader over 32-bit big-endian words, from any bit position (k_xtc_expand)
     const unsigned* wp;
@@ -134,6 +137,12 @@ constexpr int XS_BATCH = 32 / XS_LW;     // rows refilled per batch of loads in 
 constexpr int XS_SPEC = 8;               // groups looked at together (below)
 static_assert(XS_WIN % (4 * WAVE) == 0 && XS_BATCH >= 1 && WAVE % XS_BATCH == 0, "window: whole words per lane");
 
+// where and why the walk refuses a frame, for the CPU tier's damaged-stream driver to count (tests/emu/xtc_damage_main.cpp defines it before
+// including this header); nothing in the product
+#ifndef MK_XTC_PROBE
+#define MK_XTC_PROBE(frame, together, e_end, e_wide, more_atoms, more_bits, e_idx, smallidx, status)
+#endif
+
 struct XtcGroup { unsigned pos, what; }; // what = first output atom (21 bits) | smallidx of the run << 21 | small atoms << 28
 
 MK_KERNEL(64) void k_xtc_scan(const unsigned char* __restrict__ bytes, const XtcFrameDesc* __restrict__ desc, long long nframes,
@@ -164,7 +173,9 @@ MK_KERNEL(64) void k_xtc_scan(const unsigned char* __restrict__ bytes, const Xtc
         else if (smallidx < XTC_FIRST || smallidx >= XTC_NMAGIC) { st = 1; live = false; }
     }
     const unsigned full_bits = d.triple_bits ? (unsigned)d.triple_bits : (unsigned)(d.field_bits[0] + d.field_bits[1] + d.field_bits[2]);
-    const unsigned long long total_bits = (unsigned long long)((d.nbytes + 3u) / 4u) * 32ull;
+    // (the stream's nbytes bytes and not the padding that rounds them up to a word: as the host decoder, which calls a frame that
+    //  reads past them corrupt)
+    const unsigned long long total_bits = (unsigned long long)d.nbytes * 8ull;
     XtcGroup* __restrict__ grp = groups + (size_t)(f < nframes ? f : 0) * (size_t)(natoms + XS_SPEC);
     unsigned pos = 0u;
     int w = 0, g = 0, run = 0;
@@ -229,6 +240,7 @@ MK_KERNEL(64) void k_xtc_scan(const unsigned char* __restrict__ bytes, const Xtc
             smallidx += step;
             const bool e_idx = (unsigned)(smallidx - XTC_FIRST) >= (unsigned)(XTC_NMAGIC - XTC_FIRST);
             st = e_end ? 1 : (e_wide ? 2 : ((e_more || e_idx) ? 1 : 0));
+            MK_XTC_PROBE(f, together, e_end, e_wide, w > (int)natoms, next > tot, e_idx, smallidx, st);
             live = st == 0 && w != (int)natoms;
         };
         // (two loops, not one with the step above under a condition: with both in one loop the compiler's exec-mask
@@ -256,8 +268,9 @@ MK_KERNEL(64) void k_xtc_scan(const unsigned char* __restrict__ bytes, const Xtc
                                     (w + (j + 1) * per <= (int)natoms);
                     open = open & ok;
                     np += open ? 1 : 0;
-                    // (written whether taken or not: the frame's records have XS_SPEC of slack, and what is not taken is
-                    // overwritten by the next step or lies beyond the frame's count)
+                    // (written whether taken or not: the frame's records have XS_SPEC of slack -- g <= w < natoms here, so
+                    // g + j < natoms + XS_SPEC --, and what is not taken is overwritten by the next step or lies beyond the
+                    // frame's count; tests/test_xtc_damage.py: the record buffer at exactly that size under AddressSanitizer)
                     grp[g + j] = XtcGroup{(unsigned)wbit + h - full_bits, (unsigned)(w + j * per) | ((unsigned)smallidx << 21) | ((unsigned)ns << 28)};
                 }
                 g += np;
@@ -272,6 +285,8 @@ MK_KERNEL(64) void k_xtc_scan(const unsigned char* __restrict__ bytes, const Xtc
         // a lane that is done -- or dead: a corrupt frame's last step may have put `rel` up to a group's length past the end of
         // its stream -- keeps taking part in the refills (the wave refills all 64 rows while any lane is live): from the start
         // of the byte buffer, so that nothing is read beyond the MKAMD_XTC_PAD bytes the header asks for behind the last record
+        // (tests/test_xtc_damage.py: refused frames in waves of live ones, the byte buffer at exactly its size under AddressSanitizer;
+        // without this line that run reports a read behind the buffer)
         if (!live) { pos = 0u; d.data_off = 0ull; }
         const unsigned long long voters = mk_ballot(live), ayes = mk_ballot(live && n_clear >= 3 * n_set);
         together = voters != 0ull && 2 * mk_popc64(ayes) >= mk_popc64(voters);

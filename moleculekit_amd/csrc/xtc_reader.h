@@ -48,15 +48,28 @@ constexpr int32_t FRAME_MAGIC = 1995;
 
 enum Status { OK = 0, E_OPEN = 1, E_FORMAT = 2, E_RANGE = 3 };
 
+// every refusal of a file or a frame below goes through this with the name of its site, so that the CPU tier's damaged-stream driver
+// (tests/emu/xtc_damage_main.cpp, which defines it before including this header) can count which ones its inputs reach
+#ifndef MKAMD_XTC_REFUSE
+#define MKAMD_XTC_REFUSE(site) (E_FORMAT)
+#endif
+
 struct Mapped {
     const uint8_t* p = nullptr;
     size_t n = 0;
     int fd = -1;
     long long ident[7] = {0, 0, 0, 0, 0, 0, 0};   // device, inode, size, mtime and ctime (s, ns): what the frame index is remembered by
+    bool owned = true;                            // false: p / n describe memory of the caller's (view), nothing is unmapped
     ~Mapped()
     {
-        if (p) munmap(const_cast<uint8_t*>(p), n);
+        if (p && owned) munmap(const_cast<uint8_t*>(p), n);
         if (fd >= 0) close(fd);
+    }
+    // the n bytes at q as the file's contents: index_frames / decode_frame / read_mapped on a buffer the caller owns and keeps alive
+    // (tests/emu/xtc_damage_main.cpp: a heap copy of exactly n bytes, whose ends a sanitizer guards -- those of a file mapping it does not)
+    void view(const uint8_t* q, size_t bytes)
+    {
+        p = q; n = bytes; owned = false;
     }
     bool open_file(const char* path)
     {
@@ -93,9 +106,9 @@ inline int index_frames(const Mapped& m, std::vector<size_t>& offs, int64_t& nat
     natoms = 0;
     size_t p = 0;
     while (p + 16 + 36 + 4 <= m.n) {
-        if (be_i32(m.p + p) != FRAME_MAGIC) return offs.empty() ? E_FORMAT : OK;
+        if (be_i32(m.p + p) != FRAME_MAGIC) return offs.empty() ? MKAMD_XTC_REFUSE("index: magic of the first frame") : OK;
         const int32_t na = be_i32(m.p + p + 4);
-        if (na < 0) return E_FORMAT;
+        if (na < 0) return MKAMD_XTC_REFUSE("index: atom count < 0");
         if (offs.empty()) natoms = na;
         size_t q = p + 16 + 36 + 4;
         if (na <= 9) {
@@ -103,7 +116,7 @@ inline int index_frames(const Mapped& m, std::vector<size_t>& offs, int64_t& nat
         } else {
             if (q + 36 > m.n) break;
             const int32_t nbytes = be_i32(m.p + q + 32);
-            if (nbytes < 0) return E_FORMAT;
+            if (nbytes < 0) return MKAMD_XTC_REFUSE("index: nbytes < 0");
             q += 36 + (((size_t)nbytes + 3) / 4) * 4;
         }
         if (q > m.n) break;
@@ -237,12 +250,12 @@ inline int decode_frame(const Mapped& m, size_t rec, int64_t natoms, int64_t F, 
                         int64_t ccol, float* box, float* time, int32_t* step)
 {
     const uint8_t* q = m.p + rec;
-    if (be_i32(q) != FRAME_MAGIC) return E_FORMAT;
-    if ((int64_t)be_i32(q + 4) != natoms) return E_FORMAT;
+    if (be_i32(q) != FRAME_MAGIC) return MKAMD_XTC_REFUSE("frame: magic");
+    if ((int64_t)be_i32(q + 4) != natoms) return MKAMD_XTC_REFUSE("frame: first atom count");
     step[col] = be_i32(q + 8);
     time[col] = be_f32(q + 12);
     for (int i = 0; i < 9; ++i) box[(size_t)i * F + col] = be_f32(q + 16 + 4 * i);
-    if ((int64_t)be_i32(q + 52) != natoms) return E_FORMAT;
+    if ((int64_t)be_i32(q + 52) != natoms) return MKAMD_XTC_REFUSE("frame: second atom count");
     q += 56;
     auto put = [&](int64_t atom, int axis, float v) { coords[((size_t)atom * 3 + axis) * (size_t)cstride + (size_t)ccol] = v; };
     if (natoms <= 9) {
@@ -256,15 +269,15 @@ inline int decode_frame(const Mapped& m, size_t rec, int64_t natoms, int64_t F, 
     int smallidx = be_i32(q + 28);
     const int32_t nbytes = be_i32(q + 32);
     q += 36;
-    if (nbytes < 0 || q + nbytes > m.p + m.n) return E_FORMAT;
+    if (nbytes < 0 || q + nbytes > m.p + m.n) return MKAMD_XTC_REFUSE("frame: nbytes");
     uint32_t range[3];
     for (int d = 0; d < 3; ++d) range[d] = (uint32_t)hi[d] - (uint32_t)lo[d] + 1u;
-    if (!range[0] || !range[1] || !range[2]) return E_FORMAT;
+    if (!range[0] || !range[1] || !range[2]) return MKAMD_XTC_REFUSE("frame: range 0");
     int field_bits[3] = {0, 0, 0}, triple_bits = 0;
     const bool wide = (range[0] | range[1] | range[2]) > 0xffffffu;
     if (wide) for (int d = 0; d < 3; ++d) field_bits[d] = bits_for(range[d]);
     else triple_bits = bits_for_product(range);
-    if (smallidx < FIRST || smallidx >= NMAGIC) return E_FORMAT;
+    if (smallidx < FIRST || smallidx >= NMAGIC) return MKAMD_XTC_REFUSE("frame: header smallidx");
     int smaller = MAGIC[std::max(FIRST, smallidx - 1)] / 2;
     int smallnum = MAGIC[smallidx] / 2;
     uint32_t small_radix[3] = {(uint32_t)MAGIC[smallidx], (uint32_t)MAGIC[smallidx], (uint32_t)MAGIC[smallidx]};
@@ -302,18 +315,18 @@ inline int decode_frame(const Mapped& m, size_t rec, int64_t natoms, int64_t F, 
                 for (int d = 0; d < 3; ++d) nxt[d] = (int32_t)((uint32_t)nxt[d] + (uint32_t)prev[d] - (uint32_t)smallnum);
                 if (k == 0) {
                     // the first small atom goes out BEFORE the full-precision one it was coded against ...
-                    if (!emit(nxt)) return E_FORMAT;
-                    if (!emit(prev)) return E_FORMAT;
+                    if (!emit(nxt)) return MKAMD_XTC_REFUSE("stream: more atoms than announced");
+                    if (!emit(prev)) return MKAMD_XTC_REFUSE("stream: more atoms than announced");
                 } else {
-                    if (!emit(nxt)) return E_FORMAT;
+                    if (!emit(nxt)) return MKAMD_XTC_REFUSE("stream: more atoms than announced");
                 }
                 for (int d = 0; d < 3; ++d) prev[d] = nxt[d];   // ... and every small atom is the reference of the next
             }
         } else {
-            if (!emit(cur)) return E_FORMAT;
+            if (!emit(cur)) return MKAMD_XTC_REFUSE("stream: more atoms than announced");
         }
         smallidx += step_idx;
-        if (smallidx < FIRST || smallidx >= NMAGIC) return E_FORMAT;
+        if (smallidx < FIRST || smallidx >= NMAGIC) return MKAMD_XTC_REFUSE(smallidx < FIRST ? "stream: smallidx below the table" : "stream: smallidx above the table");
         if (step_idx < 0) {
             smallnum = smaller;
             smaller = smallidx > FIRST ? MAGIC[smallidx - 1] / 2 : 0;
@@ -322,9 +335,9 @@ inline int decode_frame(const Mapped& m, size_t rec, int64_t natoms, int64_t F, 
             smallnum = MAGIC[smallidx] / 2;
         }
         small_radix[0] = small_radix[1] = small_radix[2] = (uint32_t)MAGIC[smallidx];
-        if (small_radix[0] == 0u || br.overrun) return E_FORMAT;
+        if (small_radix[0] == 0u || br.overrun) return MKAMD_XTC_REFUSE("stream: overrun");
     }
-    return (w == natoms) ? OK : E_FORMAT;
+    return (w == natoms) ? OK : MKAMD_XTC_REFUSE("stream: atoms missing");
 }
 
 // natoms / nframes of a file
@@ -366,6 +379,9 @@ inline void prefault_output(float* p, size_t n_floats, int nthreads)
     for (auto& th : pool) th.join();
 }
 
+inline int read_mapped(const Mapped& m, const FrameIndex& index, const int64_t* sel, int64_t nsel, int64_t natoms_expected, float* coords,
+                       float* box, float* time, int32_t* step, int nthreads, std::string& err);
+
 // Decode `nsel` frames (indices `sel`, or 0..nsel-1 when sel == nullptr) into frame-fastest arrays of width nsel.
 inline int read(const char* path, const int64_t* sel, int64_t nsel, int64_t natoms_expected, float* coords, float* box,
                 float* time, int32_t* step, int nthreads, std::string& err)
@@ -375,8 +391,15 @@ inline int read(const char* path, const int64_t* sel, int64_t nsel, int64_t nato
     std::shared_ptr<const FrameIndex> idx;
     int st = index_frames_cached(m, idx);
     if (st != OK) { err = "not an XTC file (bad magic number)"; return st; }
-    const std::vector<size_t>& offs = idx->offs;
-    const int64_t natoms = idx->natoms;
+    return read_mapped(m, *idx, sel, nsel, natoms_expected, coords, box, time, step, nthreads, err);
+}
+
+// read() behind the open and the frame index: the same on a file mapping and on a view of the caller's bytes
+inline int read_mapped(const Mapped& m, const FrameIndex& index, const int64_t* sel, int64_t nsel, int64_t natoms_expected, float* coords,
+                       float* box, float* time, int32_t* step, int nthreads, std::string& err)
+{
+    const std::vector<size_t>& offs = index.offs;
+    const int64_t natoms = index.natoms;
     if (natoms != natoms_expected) { err = "atom count of the file differs from the buffers'"; return E_RANGE; }
     for (int64_t j = 0; j < nsel; ++j) {
         const int64_t f = sel ? sel[j] : j;

@@ -320,3 +320,180 @@ def test_gpu_random_sweep_of_reference_written_files(hip_ctx, tmp_path):
         n_dev += _dev_check(fn, rc, rb, rt, rs, N, hip_ctx)
         os.remove(fn)
     assert n_dev >= 150
+
+
+# ------------------------------------------------------------------------------------------------
+# GPU tier: damaged files.  ONLY the cases of tests/golden/xtc_damage_cases.json: inputs on which tests/emu/xtc_damage_main.cpp ran
+# this kernel source under the host sanitizers and found every access in bounds (tests/test_xtc_damage.py regenerates the list and
+# compares it).  No other damage goes to the device.
+# ------------------------------------------------------------------------------------------------
+GOLDEN = os.path.dirname(FIX)
+DAMAGE_CASES = os.path.join(GOLDEN, "xtc_damage_cases.json")
+
+
+def _damage_cases():
+    import json
+    with open(DAMAGE_CASES) as f:
+        return json.load(f)
+
+
+def _fixture_path(name):
+    for d in (FIX, os.path.join(GOLDEN, "xtc")):
+        if os.path.exists(os.path.join(d, name + ".xtc")):
+            return os.path.join(d, name + ".xtc")
+    raise FileNotFoundError(name)
+
+
+def _damaged_file(case, tmp_path):
+    buf = bytearray(open(_fixture_path(case["fixture"]), "rb").read())
+    for off, hexbytes in case["patch"]:
+        b = bytes.fromhex(hexbytes)
+        buf[off:off + len(b)] = b
+    if case["cut"] is not None:
+        del buf[case["cut"]:]
+    buf += bytes.fromhex(case["append"])
+    fn = str(tmp_path / f"damaged_{case['id']}_{len(case['selection'])}.xtc")
+    with open(fn, "wb") as f:
+        f.write(bytes(buf))
+    return fn
+
+
+def _expected(case):
+    """-> (selection inside the frame index, the message the device path must raise or None, the statuses of that selection)."""
+    keep = [j for j, p in enumerate(case["parser"]) if p != 2]
+    sel = np.array([case["selection"][j] for j in keep], np.int64)
+    parser = [case["parser"][j] for j in keep]
+    dev = [case["device"][j] for j in keep]
+    if 1 in parser:
+        return sel, "parser", dev
+    bad = [j for j, s in enumerate(dev) if s]
+    if bad:                                          # (the error names the first refused frame of the selection)
+        return sel, f"frame {int(sel[bad[0]])} is " + ("corrupt" if dev[bad[0]] == 1 else "outside what the device decoder takes"), dev
+    return sel, None, dev
+
+
+@pytest.mark.gpu
+def test_gpu_damaged_files_of_the_sanitized_list(hip_ctx, tmp_path):
+    """read_xtc_frames_dev on every listed damaged file: a RuntimeError saying "corrupt" or "outside what the device decoder takes"
+    exactly where the list has a status 1 or 2 (the parser's own refusal is the library's ValueError "corrupt XTC frame"), the listed number of frames in the index, and otherwise the
+    listed CRC-32 of the output and the host decoder's bits."""
+    import zlib
+    cases = _damage_cases()
+    assert len(cases) >= 24
+    n_raised = n_decoded = 0
+    for case in cases:
+        fn = _damaged_file(case, tmp_path)
+        tag = (case["id"], case["fixture"], case["damage"], case["selection_name"])
+        if case["index_status"]:
+            with pytest.raises((RuntimeError, ValueError)):
+                xtc.get_xtc_nframes(fn)
+            os.remove(fn)
+            continue
+        assert xtc.get_xtc_nframes(fn) == case["frames_indexed"], tag
+        sel, message, dev = _expected(case)
+        if len(sel) == 0:
+            os.remove(fn)
+            continue
+        if message == "parser":                      # (the headers: an invalid argument of the library's, before anything reaches the device)
+            with pytest.raises(ValueError, match="corrupt XTC frame"):
+                xtc.read_xtc_frames_dev(fn, sel, scale=1.0, ctx=hip_ctx)
+            n_raised += 1
+        elif message is not None:
+            with pytest.raises(RuntimeError, match=message):
+                xtc.read_xtc_frames_dev(fn, sel, scale=1.0, ctx=hip_ctx)
+            n_raised += 1
+        else:
+            got = xtc.read_xtc_frames_dev(fn, sel, scale=1.0, ctx=hip_ctx)[0].cpu().numpy()
+            assert zlib.crc32(np.ascontiguousarray(got).tobytes()) == case["crc32"], tag
+            host = _fm(xtc.read_xtc_frames(fn, sel)[0])
+            assert np.array_equal(got.view(np.uint32), host.view(np.uint32)), tag
+            n_decoded += 1
+        os.remove(fn)
+    assert n_raised >= 16 and n_decoded >= 5
+
+
+@pytest.mark.gpu
+def test_gpu_iter_voxelize_xtc_on_damaged_files(hip_ctx, tmp_path):
+    """iterVoxelizeXTC over three listed cases (one the walk calls corrupt, one it leaves to the host, one both decoders take) with each
+    decode mode, the selection as ONE chunk: it raises or yields as the list says -- "host" by the host decoder's verdict --, yields no
+    features for a refused chunk, and leaves the context usable: the undamaged fixture decodes to its bits afterwards."""
+    import torch
+    from moleculekit_amd import batch
+    cases = _damage_cases()
+    picked = []
+    for want in (1, 2, 0):
+        for case in cases:
+            sel, message, dev = _expected(case)
+            inside = len(sel) and not case["index_status"] and 1 not in case["parser"] and case["selection_name"] == "neighbours"
+            if inside and ((want and dev.count(want) and (" is corrupt" if want == 1 else " is outside") in (message or "")) or
+                           (not want and message is None)):
+                picked.append(case)
+                break
+    assert len(picked) == 3
+    for case in picked:
+        fn = _damaged_file(case, tmp_path)
+        sel, message, dev = _expected(case)
+        N = xtc.get_xtc_natoms(fn)
+        host_ok = all(h == 0 for h, p in zip(case["host"], case["parser"]) if p != 2)
+        sig = np.full((N, 2), 1.5)
+        center = np.zeros(3)
+        feats = {}
+        for decode in ("gpu", "auto", "host"):
+            contiguous = np.array_equal(sel, np.arange(sel[0], sel[0] + len(sel)))
+            on_device = decode == "gpu" or (decode == "auto" and contiguous and
+                                            xtc.device_decodable(xtc.chunk_desc(fn, sel[:1], N)[0], N))
+            refused = (message is not None) if on_device else not host_ok
+            out = []
+            gen = batch.iterVoxelizeXTC(fn, sig, center, [8, 8, 8], 1.0, pbc=False, frames=sel, chunk=len(sel), decode=decode, ctx=hip_ctx)
+            if refused:
+                with pytest.raises(RuntimeError if on_device else (RuntimeError, ValueError)):
+                    for _, f in gen:
+                        out.append(f)
+                assert not out, (case["id"], decode)
+            else:
+                for _, f in gen:
+                    out.append(f)
+                torch.cuda.synchronize()
+                feats[decode] = torch.cat(out).cpu().numpy()
+        vals = list(feats.values())
+        for v in vals[1:]:
+            assert np.array_equal(v, vals[0]), case["id"]
+        # the context afterwards
+        good = _fixture_path(case["fixture"])
+        g = xtc.read_xtc_frames_dev(good, sel, scale=1.0, ctx=hip_ctx)
+        assert np.array_equal(g[0].cpu().numpy().view(np.uint32), _fm(xtc.read_xtc_frames(good, sel)[0]).view(np.uint32)), case["id"]
+
+
+@pytest.mark.gpu
+def test_gpu_iter_voxelize_xtc_refused_chunk_among_chunks_in_flight(hip_ctx, tmp_path):
+    """iterVoxelizeXTC(decode="gpu") with ONE frame per chunk over a listed file whose damaged frame the walk calls corrupt: three chunks
+    of an undamaged neighbour, the damaged frame, four more of the neighbour -- the refused chunk has chunks before and behind it in
+    flight.  The error names the damaged frame, no chunk from the damaged one on is yielded, and what is yielded are the features of the
+    undamaged file's frame (decode="host"), bit for bit.  Every chunk is a selection the sanitized list has: a frame alone."""
+    import torch
+    from moleculekit_amd import batch
+    fit = [c for c in _damage_cases()
+           if c["selection_name"] == "neighbours" and not c["index_status"] and set(c["parser"]) == {0} and c["device"].count(1) == 1
+           and c["device"].count(0) >= 1 and c["host"][c["device"].index(1)] != 0]
+    case = ([c for c in fit if c["kind"].startswith("stream")] or fit)[0]        # (a refusal inside the walk, if the list has one)
+    fn = _damaged_file(case, tmp_path)
+    bad = case["selection"][case["device"].index(1)]
+    good = case["selection"][case["device"].index(0)]
+    N = xtc.get_xtc_natoms(fn)
+    sig, center = np.full((N, 2), 1.5), np.zeros(3)
+    frames = np.array([good] * 3 + [bad] + [good] * 4, np.int64)
+    ref = [f for _, f in batch.iterVoxelizeXTC(_fixture_path(case["fixture"]), sig, center, [8, 8, 8], 1.0, pbc=False, frames=frames[:1],
+                                               decode="host", ctx=hip_ctx)]
+    torch.cuda.synchronize()
+    ref = ref[0].cpu().numpy()
+    got = []
+    with pytest.raises(RuntimeError, match=f"frame {bad} is corrupt"):
+        for idx, f in batch.iterVoxelizeXTC(fn, sig, center, [8, 8, 8], 1.0, pbc=False, frames=frames, chunk=1, decode="gpu", ctx=hip_ctx):
+            got.append((np.array(idx), f))
+    torch.cuda.synchronize()
+    assert len(got) <= 3, [i for i, _ in got]
+    for idx, f in got:
+        assert idx.tolist() == [good]
+        assert np.array_equal(f.cpu().numpy(), ref), case["id"]
+    g = xtc.read_xtc_frames_dev(_fixture_path(case["fixture"]), frames[:4], scale=1.0, ctx=hip_ctx)     # the context afterwards
+    assert np.array_equal(g[0].cpu().numpy().view(np.uint32), _fm(xtc.read_xtc_frames(_fixture_path(case["fixture"]), frames[:4])[0]).view(np.uint32))
