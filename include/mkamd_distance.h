@@ -108,6 +108,8 @@ int mkamd_selftest_sqrt(mkamd_ctx* ctx, uint64_t* mismatches, uint32_t* first_ba
  * kernel instead of the row kernel with the selections swapped (lanes along the first selection, transposed stores).
  * 256 / 512: shell counts do not take their frame-lane / atom-lane kernel; 1024 / 2048: the dihedral angles the same.
  * 4096 / 8192: the group moments do not take the form in which a lane group owns a whole (frame, group) / the segmented form.
+ * 16384 / 32768: the periodic wrap does not take the lane-per-group kernel (every group a wave) / the wave-per-group kernel (every
+ * group a lane).
  * Calls of at most 32 frames take the row kernel wherever it applies (its lanes
  * run along the second atoms; the other kernels' along frames).  Every kernel produces the same
  * bits; for tests (every kernel over the same shapes) and same-box A-B timing. */
@@ -272,6 +274,36 @@ int mkamd_group_moments_host(mkamd_ctx* ctx, const float* coords, int64_t n_atom
 int mkamd_fluctuation_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const uint32_t* alnsel,
                            const float* alnref, int64_t n_aln, const uint32_t* atoms, int64_t n_sel, const uint32_t* offsets,
                            int64_t n_groups, const double* ref, double* out);
+
+/* ---- periodic wrap: every bonded group of every frame back into the rectangular cell around a centre (moleculekit
+ * wrapping/wrapping.pyx wrap_box, called from Molecule.wrap with boxangles of 90) ----
+ * Device layout: frame-major float32 d_xyz [n_frames, n_atoms, 3], d_box float32 [3, n_frames].  Groups are contiguous runs of atoms:
+ * d_starts uint32 [n_groups + 1], starts[0] = 0, increasing, starts[n_groups] = n_atoms.  Per frame the box centre is the float32
+ * running mean c = c + (x - c) / float(n + 1) over the atoms d_centersel uint32 [n_centersel] of the UNWRAPPED frame, in the order
+ * given -- or, with n_centersel == 0, the three floats `center` (host memory, read before the call returns).  Per group the same
+ * running mean over its atoms in order; per axis i, diff = group centre - box centre: where fabs(diff) > box_i / 2, every atom of
+ * the group gets x_i - float(double(box_i) * round(double(diff / box_i))) (float32 quotient, IEEE division, C's round).  Each
+ * operation is rounded on its own: the results are the reference's bits.  A zero box length, a NaN or an infinite coordinate give
+ * what that arithmetic gives.  d_out may be d_xyz (in place: groups that do not move are not written; the centres are complete
+ * before any group is written) or a separate array of the same shape (every atom is written).
+ * d_large uint32 [n_large]: the groups of more than mkamd_wrap_small_max(ctx) atoms, which a wave each handles instead of a lane
+ * (a group listed that is not one is skipped; one that is missing is not wrapped).
+ * MKAMD_EINVAL: a NULL pointer, a negative size, n_atoms or n_frames >= 2^30, more groups than atoms; (host form) starts that do not
+ * begin at 0, do not increase or do not end at the number of atoms, an index >= n_atoms, rows that do not increase, a centre atom
+ * that is not among the rows.  The device form does not check indices (they are device memory) but never reads or writes past
+ * n_atoms: group bounds are clamped, a centre index >= n_atoms reads as NaN. */
+int64_t mkamd_wrap_small_max(mkamd_ctx* ctx);
+/* asynchronous on the context's stream */
+int mkamd_wrap_box_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, int64_t n_frames, const float* d_box, const uint32_t* d_starts,
+                       int64_t n_groups, const uint32_t* d_large, int64_t n_large, const uint32_t* d_centersel, int64_t n_centersel,
+                       const float* center, float* d_out);
+/* host arrays: coords float32 [n_atoms, 3, n_frames] (Molecule.coords), box [3, n_frames].  rows NULL: every atom travels, starts
+ * [n_groups + 1] end at n_atoms and out is [n_atoms, 3, n_frames] (it may be coords).  rows uint32 [n_rows], strictly increasing: only
+ * these atoms' rows are packed and uploaded (csrc/host_pack.h); starts then cut the ROWS into groups (they end at n_rows) and out is
+ * [n_rows, 3, n_frames].  centersel names atoms of coords in either case (each must be among the rows).  Returns when out is filled. */
+int mkamd_wrap_box_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const float* box, const uint32_t* rows,
+                        int64_t n_rows, const uint32_t* starts, int64_t n_groups, const uint32_t* centersel, int64_t n_centersel,
+                        const float* center, float* out);
 
 #ifdef __cplusplus
 }

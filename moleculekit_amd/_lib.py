@@ -136,6 +136,10 @@ SIGNATURES = {
     "mkamd_fluctuation_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _vp, _vp]),
     "mkamd_group_moments_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_int, _vp]),
     "mkamd_fluctuation_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
+    # include/mkamd_distance.h, periodic wrap
+    "mkamd_wrap_small_max": (_c_i64, [_vp]),
+    "mkamd_wrap_box_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
+    "mkamd_wrap_box_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
 }
 
 _lib = None
@@ -373,7 +377,7 @@ class Context:
     def set_dist_kernels(self, avoid_mask: int = 0):
         """Kernels dist_trajectory must NOT take (include/mkamd_distance.h): 1 block-per-frame, 2 rows, 4 rectangular tiles, 8 the
         row kernel's 16-byte stores; 16: the row kernel wherever it applies; 32: host calls upload the whole coordinate array (no packing
-        of the selected atoms' rows); 64: selfdist calls keep the pair-table kernel (no triangular row kernel); 128: short-row calls of few frames keep the tile kernel (no swapped row kernel); 256 / 512: shell counts avoid their frame-lane / atom-lane kernel; 1024 / 2048: dihedrals the same; 4096 / 8192: group moments avoid the form in which a lane group owns a (frame, group) / the segmented form; 0 = free choice.  Same bits whichever runs (tests, A-B timing)."""
+        of the selected atoms' rows); 64: selfdist calls keep the pair-table kernel (no triangular row kernel); 128: short-row calls of few frames keep the tile kernel (no swapped row kernel); 256 / 512: shell counts avoid their frame-lane / atom-lane kernel; 1024 / 2048: dihedrals the same; 4096 / 8192: group moments avoid the form in which a lane group owns a (frame, group) / the segmented form; 16384 / 32768: the periodic wrap avoids its lane-per-group / wave-per-group kernel; 0 = free choice.  Same bits whichever runs (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_dist_kernels(self._h, int(avoid_mask)))
 
     def set_reduction_block(self, block: int = 0):

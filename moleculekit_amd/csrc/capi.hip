@@ -14,6 +14,7 @@
 #include "shell_pipeline.h"
 #include "dihedral_pipeline.h"
 #include "moments_pipeline.h"
+#include "wrap_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "xtc_headers.h"
@@ -711,7 +712,7 @@ try {
 int mkamd_ctx_set_dist_kernels(mkamd_ctx* ctx, int avoid_mask)
 try {
     if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
-    if (avoid_mask < 0 || avoid_mask > 16383) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel), 256 / 512 (shell counts: not the frame-lane / not the atom-lane kernel), 1024 / 2048 (dihedrals: the same), 4096 / 8192 (group moments: not the form in which a lane group owns a (frame, group) / not the segmented form)");
+    if (avoid_mask < 0 || avoid_mask > 65535) return fail(MKAMD_EINVAL, "avoid mask: bits 1 (block-per-frame kernel), 2 (row kernel), 4 (rectangular tile kernel), 8 (16-byte row stores), 16 (the row kernel wherever it applies), 32 (host calls upload the whole coordinate array), 64 (selfdist calls keep the pair-table kernel), 128 (short-row calls of few frames keep the tile kernel), 256 / 512 (shell counts: not the frame-lane / not the atom-lane kernel), 1024 / 2048 (dihedrals: the same), 4096 / 8192 (group moments: not the form in which a lane group owns a (frame, group) / not the segmented form), 16384 / 32768 (periodic wrap: not the lane-per-group / not the wave-per-group kernel)");
     ctx->dist_avoid = avoid_mask;
     return MKAMD_OK;
 } MK_API_CATCH
@@ -2394,6 +2395,70 @@ try {
                                (const uint32_t*)in.doffs, G, in.max_group, (const double*)dref, (double*)dout);
     if (st) return st;
     return download(ctx, out, dout, bytes, false);
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// periodic wrap (include/mkamd_distance.h "periodic wrap"; wrap_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int64_t mkamd_wrap_small_max(mkamd_ctx* ctx) { return (int64_t)mkamd::wrap_small_max(ctx ? (ctx->dist_avoid >> 14) & 3 : 0); }
+
+extern "C" int mkamd_wrap_box_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const float* d_box, const uint32_t* d_starts, int64_t G,
+                                  const uint32_t* d_large, int64_t n_large, const uint32_t* d_centersel, int64_t n_c, const float* center,
+                                  float* d_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (n_c == 0 && !center && N > 0 && F > 0 && G > 0) return fail(MKAMD_EINVAL, "NULL pointer (neither a centre selection nor a centre)");
+    mkamd::WrapArgs a;
+    a.xyz = d_xyz; a.n_atoms = N; a.n_frames = F; a.box = d_box; a.starts = d_starts; a.n_groups = G; a.large = d_large; a.n_large = n_large;
+    a.centersel = d_centersel; a.n_centersel = n_c; a.out = d_out;
+    if (n_c == 0 && center) { a.center[0] = center[0]; a.center[1] = center[1]; a.center[2] = center[2]; }
+    std::string err;
+    st = mkamd::run_wrap_box(*ctx, a, err, (ctx->dist_avoid >> 14) & 3);
+    return run_status(st, err);
+} MK_API_CATCH
+
+extern "C" int mkamd_wrap_box_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const float* box, const uint32_t* rows, int64_t n_rows,
+                                   const uint32_t* starts, int64_t G, const uint32_t* centersel, int64_t n_c, const float* center, float* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || G < 0 || n_c < 0 || n_rows < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (N > 0x3fffffffLL || F > 0x3fffffffLL) return fail(MKAMD_EINVAL, "too many atoms or frames (>= 2^30)");
+    const int64_t M = rows ? n_rows : N;                             // atoms that travel
+    if (F == 0 || M == 0) return MKAMD_OK;
+    if (!coords || !box || !out || (n_c > 0 && !centersel) || (n_c == 0 && !center)) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (rows) {
+        if ((st = check_indices(rows, n_rows, N, "rows: atom"))) return st;
+        for (int64_t k = 1; k < n_rows; ++k)
+            if (rows[k] <= rows[k - 1]) return fail(MKAMD_EINVAL, "rows must be strictly increasing atom indices");
+    }
+    if (const char* e = mkamd::wrap_check_starts(starts, G, M)) return fail(MKAMD_EINVAL, e);
+    if ((st = check_indices(centersel, n_c, N, "centersel: atom"))) return st;
+    if (rows)
+        for (int64_t k = 0; k < n_c; ++k)
+            if (!std::binary_search(rows, rows + n_rows, centersel[k])) return fail(MKAMD_EINVAL, "centersel names an atom that is not among the rows");
+    HostStage up(ctx, coords, N, F, {{rows, n_rows}}, /*always=*/rows != nullptr);
+    void *dxyz, *dslab, *dbox, *dstarts, *dlarge = nullptr, *dsel = nullptr;
+    if ((st = upload_frame_major(ctx, WS_A_SLAB, WS_A_XYZ, up.host_rows(), 3 * M, F, &dxyz))) return st;
+    const int64_t small_max = mkamd_wrap_small_max(ctx);
+    std::vector<uint32_t> large;
+    for (int64_t g = 0; g < G; ++g)
+        if ((int64_t)starts[g + 1] - (int64_t)starts[g] > small_max) large.push_back((uint32_t)g);
+    if ((st = upload(ctx, WS_W_STARTS, starts, (size_t)(G + 1) * 4, &dstarts))) return st;
+    if (!large.empty() && (st = upload(ctx, WS_W_LARGE, large.data(), large.size() * 4, &dlarge))) return st;
+    if (n_c > 0 && (st = up.list_to(WS_W_SEL, centersel, n_c, &dsel))) return st;
+    if ((st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &dbox))) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                      // (`large`, the packed rows and the rewritten selection are read by then)
+    up.held.clear();
+    st = mkamd_wrap_box_dev(ctx, (const float*)dxyz, M, F, (const float*)dbox, (const uint32_t*)dstarts, G, (const uint32_t*)dlarge,
+                            (int64_t)large.size(), (const uint32_t*)dsel, n_c, center, (float*)dxyz);
+    if (st) return st;
+    // back to the reference's [M][3][F]
+    const size_t bytes = (size_t)3 * M * F * 4;
+    if ((st = ctx->ensure(WS_A_SLAB, bytes, &dslab))) return st;
+    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dxyz, F, 3 * M, 3 * M, 1.0f, (float*)dslab))) return st;
+    return download(ctx, out, dslab, bytes, true);
 } MK_API_CATCH
 
 #ifdef MK_PHASE_TIMERS

@@ -46,6 +46,8 @@ enum WsSlot {
     WS_S_POINTS, WS_S_PACK, WS_S_AREA, WS_S_ERR, WS_S_SLAB, WS_S_XYZ, WS_S_RADII, WS_S_MAP, WS_S_MASK, WS_S_OUT,
     // group moments (moments_pipeline.h) and their host entry points
     WS_M_PART, WS_M_REF, WS_M_ATOMS, WS_M_OFFS, WS_M_W, WS_M_REFIN,
+    // periodic wrap (wrap_pipeline.h) and its host entry point
+    WS_W_CENTRE, WS_W_STARTS, WS_W_LARGE, WS_W_SEL,
     WS_NSLOTS
 };
 

@@ -13,8 +13,12 @@ the aligned trajectory is never materialised.
 * ``MetricCoordinate``, ``MetricGyration``, ``MetricFluctuation``, ``MetricSphericalCoordinate`` -- the reference's projections
   (``project`` / ``getMapping``); ``install()`` / ``uninstall()`` swap ``project`` of an installed moleculekit's four classes.
 
-Periodic wrapping is NOT done on the device: with ``pbc=True`` (the reference's default) and a box that is not all zeros ``project``
-raises ``NotImplementedError``.  There is no CPU path: without the library or a device every entry point raises.
+Periodic wrapping (the reference's ``mol.wrap(centersel)`` in front of the alignment) is on the device too (``moleculekit_amd.wrap``),
+and opt-in here: by default ``pbc=True`` (the reference's default) with a box that is not all zeros still raises
+``NotImplementedError``, as before; with ``wrap_on_device=True`` ``project`` first wraps -- only the centre selection and the bonded
+groups (``mol.bonds``) of the atoms the projection and its alignment name travel -- and goes on with the wrapped atoms on the device.
+Once ``wrap.install()`` has swapped ``Molecule.wrap``, the installed-mode projections below wrap on the device with no change here.
+There is no CPU path: without the library or a device every entry point raises.
 """
 from __future__ import annotations
 
@@ -280,14 +284,19 @@ def _sel(mol, sel, name, message):
     return m
 
 
-def _check_pbc(mol, pbc):
-    """the pbc rule: wrapping is not on the device.  A missing or all-zero box makes ``pbc=True`` the no-op it is in the reference."""
+def _needs_wrap(mol, pbc):
+    """``pbc`` with a box that is there and not all zeros (a missing or all-zero box makes ``pbc=True`` the no-op it is in the reference)"""
     if not pbc:
-        return
+        return False
     box = getattr(mol, "box", None)
-    if box is None or np.size(box) == 0 or not np.any(np.asarray(box) != 0):
-        return
-    raise NotImplementedError("periodic wrapping is not done on the device: wrap the molecule first (Molecule.wrap) or pass pbc=False")
+    return not (box is None or np.size(box) == 0 or not np.any(np.asarray(box) != 0))
+
+
+def _check_pbc(mol, pbc):
+    """the pbc rule of the default (``wrap_on_device=False``): wrapping is not done unasked"""
+    if _needs_wrap(mol, pbc):
+        raise NotImplementedError("periodic wrapping is not done on the device: wrap the molecule first (Molecule.wrap) or pass pbc=False "
+                                  "(or construct the projection with wrap_on_device=True)")
 
 
 def _element_masses(mol, idx):
@@ -313,7 +322,8 @@ def _frame_table(cols):
 class _Aligned:
     """what the four projections share: the pbc rule and the alignment of every frame on a reference, as ``(alnsel, alnref)``"""
 
-    def _init_align(self, refmol, trajalnsel, refalnsel, centersel, pbc):
+    def _init_align(self, refmol, trajalnsel, refalnsel, centersel, pbc, wrap_on_device=False):
+        self._wrap_on_device = bool(wrap_on_device)
         self._refmol = refmol
         self._trajalnsel = trajalnsel
         self._refalnsel = refalnsel if refalnsel is not None else trajalnsel
@@ -336,21 +346,88 @@ class _Aligned:
             raise ValueError(f"trajalnsel picks {sel.size} atoms and refalnsel {refsel.size}")
         return sel, _frame0(self._refmol, refsel)
 
+    def _wrapped(self, mol, named, ctx):
+        """``None``: project ``mol.coords`` as they are (no wrapping is due).  Else ``_WrappedRows``: the trajectory wrapped on the
+        device, cut down to the atoms that matter -- ``wrap_on_device=True``; without it the pbc rule raises."""
+        if not _needs_wrap(mol, self._pbc):
+            return None
+        _check_pbc(mol, self._pbc and not self._wrap_on_device)
+        align_idx = np.zeros(0, np.int64) if self._trajalnsel is None else \
+            np.flatnonzero(_sel(mol, self._trajalnsel, "trajalnsel", "Alignment selection resulted in 0 atoms."))
+        return _WrappedRows(mol, np.flatnonzero(_sel(mol, self._centersel, "centersel", "Center selection resulted in 0 atoms.")),
+                            np.concatenate([np.asarray(named, np.int64).reshape(-1), align_idx]), ctx)
+
+    def _affine(self, mol, w):
+        """the frames' transforms on the wrapped rows ``w`` (``None``: no alignment); the reference aligns on frame 0 of the WRAPPED
+        molecule where there is no refmol"""
+        from . import align as _align_mod
+
+        if self._trajalnsel is None:
+            return None
+        sel, ref = self._align(mol)
+        rows = w.row_of(sel)
+        import torch
+
+        if self._refmol is None:
+            ref = w.xyz[0].index_select(0, torch.as_tensor(rows.astype(np.int64), device=w.xyz.device)).cpu().numpy()
+        d_ref = torch.as_tensor(np.ascontiguousarray(ref, dtype=_F32), device=w.xyz.device)
+        return _align_mod.kabsch_transforms(w.xyz, d_ref, rows, refsel=np.arange(rows.size), ctx=w.ctx)[0]
+
+
+class _WrappedRows:
+    """A molecule's trajectory wrapped on the device (``wrap.wrap_trajectory``, in place on the upload), holding only the rows that
+    matter: the centre selection and every atom of each bonded group with a named atom.  ``xyz``: CUDA float32 ``[F, M, 3]``;
+    ``row_of(atoms)``: their rows in it."""
+
+    def __init__(self, mol, centersel, named, ctx):
+        import torch
+
+        from . import wrap as _wrap
+
+        coords = _coords(np.asarray(mol.coords))
+        N, _, F = coords.shape
+        box = np.asarray(mol.box)
+        if box.shape[1] != F:
+            raise RuntimeError(_wrap._FRAMES)
+        angles = getattr(mol, "boxangles", None)
+        if angles is not None and np.size(angles) and np.any(np.asarray(angles) != 90):
+            raise NotImplementedError("the box is triclinic (boxangles != 90): the unit cells 'rectangular', 'triclinic' and 'compact' "
+                                      "of a triclinic box are not wrapped on the device")
+        starts = _wrap.bonded_groups(getattr(mol, "bonds", None), N)
+        self.rows, packed = _wrap.travel_rows(starts, named, centersel)
+        self.ctx = ctx or _lib.default_context()
+        dev = torch.device("cuda", self.ctx.device)
+        host = np.ascontiguousarray(np.transpose(coords[self.rows.astype(np.int64)], (2, 0, 1)))          # [F, M, 3]
+        self.xyz = torch.as_tensor(host, device=dev)
+        _wrap.wrap_trajectory(self.xyz, np.ascontiguousarray(box, dtype=_F32), packed, centersel=self.row_of(centersel), out=self.xyz,
+                              ctx=self.ctx)
+
+    def row_of(self, atoms):
+        return np.ascontiguousarray(np.searchsorted(self.rows, np.asarray(atoms, np.int64)), dtype=_U32)
+
+    def csr(self, groups):
+        """a list of index arrays or the (atoms, offsets) pair, in rows"""
+        if isinstance(groups, tuple):
+            return (self.row_of(groups[0]), groups[1])
+        return [self.row_of(g) for g in groups]
+
 
 class MetricCoordinate(_Aligned):
     """The reference's ``moleculekit.projections.metriccoordinate.MetricCoordinate`` on the GPU: ``project(mol)`` -> float32
     ``[numFrames, 3 n]`` (all X, then all Y, then all Z) of the atoms of ``atomsel`` or, with ``groupsel`` ``"all"`` / ``"residue"``,
     of the centroid (``groupreduce="centroid"``) or centre of mass (``"com"``, element masses as float32) of each group;
     ``getMapping(mol)``.  Selections are boolean masks or integer index arrays (``"all"`` is understood).  ``pbc=True`` (the
-    default) with a box that is not all zeros raises ``NotImplementedError``: wrapping is not on the device."""
+    default) with a box that is not all zeros raises ``NotImplementedError`` unless ``wrap_on_device=True``: every frame is then wrapped
+    on the device first, around ``centersel`` (a mask or indices) by the bonded groups of ``mol.bonds`` (``moleculekit_amd.wrap``)."""
 
-    def __init__(self, atomsel, refmol=None, trajalnsel=None, refalnsel=None, centersel="protein", groupsel=None, groupreduce="com", pbc=True):
+    def __init__(self, atomsel, refmol=None, trajalnsel=None, refalnsel=None, centersel="protein", groupsel=None, groupreduce="com", pbc=True,
+                 wrap_on_device=False):
         if atomsel is None:
             raise ValueError("Atom selection cannot be None")
         self._atomsel = atomsel
         self._groupsel = groupsel
         self._groupreduce = groupreduce
-        self._init_align(refmol, trajalnsel, refalnsel, centersel, pbc)
+        self._init_align(refmol, trajalnsel, refalnsel, centersel, pbc, wrap_on_device)
 
     def _groups(self, mol):
         """(atom indexes [n], list of groups of atom indexes or None)"""
@@ -365,7 +442,7 @@ class MetricCoordinate(_Aligned):
         raise RuntimeError("Invalid groupsel option. Can only be 'all' or 'residue'")
 
     def project(self, mol, ctx=None):
-        _check_pbc(mol, self._pbc)
+        _check_pbc(mol, self._pbc and not self._wrap_on_device)
         idx, groups = self._groups(mol)
         weights = None
         if groups is None:
@@ -374,7 +451,10 @@ class MetricCoordinate(_Aligned):
             weights = np.concatenate([_element_masses(mol, g).astype(_F32) for g in groups])
         elif self._groupreduce != "centroid":
             raise RuntimeError("Invalid groupreduce option. Can onlye be 'centroid' or 'com'")
-        return group_moments(mol.coords, groups, weights=weights, align=self._align(mol), out="center", ctx=ctx)
+        w = self._wrapped(mol, idx, ctx)
+        if w is None:
+            return group_moments(mol.coords, groups, weights=weights, align=self._align(mol), out="center", ctx=ctx)
+        return group_moments_trajectory(w.xyz, w.csr(groups), weights=weights, affine=self._affine(mol, w), out="center", ctx=w.ctx).cpu().numpy()
 
     def getMapping(self, mol):
         idx, groups = self._groups(mol)
@@ -397,11 +477,11 @@ class MetricGyration(_Aligned):
     """The reference's ``MetricGyration`` on the GPU: ``project(mol)`` -> float32 ``[numFrames, 4]``: the mass-weighted radius of
     gyration of ``atomsel`` and its components about the x, y and z axes.  ``mol.masses``, or element masses where any mass is 0."""
 
-    def __init__(self, atomsel, refmol=None, trajalnsel=None, refalnsel=None, centersel="protein", pbc=True):
+    def __init__(self, atomsel, refmol=None, trajalnsel=None, refalnsel=None, centersel="protein", pbc=True, wrap_on_device=False):
         if atomsel is None:
             raise ValueError("Atom selection cannot be None")
         self._atomsel = atomsel
-        self._init_align(refmol, trajalnsel, refalnsel, centersel, pbc)
+        self._init_align(refmol, trajalnsel, refalnsel, centersel, pbc, wrap_on_device)
 
     def _masses(self, mol, idx):
         masses = np.asarray(mol.masses)[idx]
@@ -412,9 +492,14 @@ class MetricGyration(_Aligned):
         return masses
 
     def project(self, mol, ctx=None):
-        _check_pbc(mol, self._pbc)
+        _check_pbc(mol, self._pbc and not self._wrap_on_device)
         idx = np.flatnonzero(_sel(mol, self._atomsel, "atomsel", "Atom selection resulted in 0 atoms."))
-        res = group_moments(mol.coords, [idx], weights=self._masses(mol, idx), align=self._align(mol), out="gyration", ctx=ctx)
+        w = self._wrapped(mol, idx, ctx)
+        if w is None:
+            res = group_moments(mol.coords, [idx], weights=self._masses(mol, idx), align=self._align(mol), out="gyration", ctx=ctx)
+        else:
+            res = group_moments_trajectory(w.xyz, w.csr([idx]), weights=self._masses(mol, idx), affine=self._affine(mol, w), out="gyration",
+                                           ctx=w.ctx).cpu().numpy()
         return res[:, 0, :]
 
     def getMapping(self, mol):
@@ -430,8 +515,10 @@ class MetricFluctuation(MetricCoordinate):
     (``sequenceID(mol.resid)`` over the whole molecule).  The default ``trajalnsel`` is the reference's selection STRING, which this
     package cannot evaluate: pass a mask or indices (``project`` raises ``TypeError`` otherwise)."""
 
-    def __init__(self, atomsel, refmol=None, trajalnsel="protein and name CA", refalnsel=None, centersel="protein", pbc=True, mode="atom"):
-        super().__init__(atomsel, refmol=refmol, trajalnsel=trajalnsel, refalnsel=refalnsel, centersel=centersel, pbc=pbc)
+    def __init__(self, atomsel, refmol=None, trajalnsel="protein and name CA", refalnsel=None, centersel="protein", pbc=True, mode="atom",
+                 wrap_on_device=False):
+        super().__init__(atomsel, refmol=refmol, trajalnsel=trajalnsel, refalnsel=refalnsel, centersel=centersel, pbc=pbc,
+                         wrap_on_device=wrap_on_device)
         self._mode = mode
 
     def _residues(self, mol, idx):
@@ -442,7 +529,7 @@ class MetricFluctuation(MetricCoordinate):
         return sequence_id((np.asarray(mol.resid),))[idx]
 
     def project(self, mol, ctx=None):
-        _check_pbc(mol, self._pbc)
+        _check_pbc(mol, self._pbc and not self._wrap_on_device)
         idx = np.flatnonzero(_sel(mol, self._atomsel, "atomsel", "Atom selection resulted in 0 atoms."))
         res_of = self._residues(mol, idx)
         ref = None
@@ -451,7 +538,7 @@ class MetricFluctuation(MetricCoordinate):
             refbox = getattr(self._refmol, "box", None)
             wrapref = self._pbc and not (refbox is None or np.size(refbox) == 0 or np.all(np.asarray(refbox) == 0))
             rc = MetricCoordinate(self._atomsel, refmol=self._refmol, trajalnsel=self._refalnsel, refalnsel=self._refalnsel,
-                                  centersel=self._centersel, pbc=wrapref).project(self._refmol, ctx=ctx)
+                                  centersel=self._centersel, pbc=wrapref, wrap_on_device=self._wrap_on_device).project(self._refmol, ctx=ctx)
             if rc.shape[0] != 1 or rc.shape[1] != 3 * idx.size:
                 raise ValueError(f"refmol must have one frame and the atoms of atomsel; its projection has shape {rc.shape}")
             ref = rc.reshape(3, idx.size).T.astype(_F64)
@@ -461,7 +548,10 @@ class MetricFluctuation(MetricCoordinate):
             idx, res_of = idx[order], res_of[order]
             ref = ref[order] if ref is not None else None
             groups = np.r_[0, np.flatnonzero(np.diff(res_of)) + 1, idx.size]
-        return fluctuation(mol.coords, idx, ref=ref, groups=groups, align=self._align(mol), ctx=ctx)
+        w = self._wrapped(mol, idx, ctx)
+        if w is None:
+            return fluctuation(mol.coords, idx, ref=ref, groups=groups, align=self._align(mol), ctx=ctx)
+        return fluctuation_trajectory(w.xyz, w.row_of(idx), ref=ref, groups=groups, affine=self._affine(mol, w), ctx=w.ctx).cpu().numpy()
 
     def getMapping(self, mol):
         idx = np.flatnonzero(_sel(mol, self._atomsel, "atomsel", "Atom selection resulted in 0 atoms."))
@@ -485,19 +575,23 @@ class MetricSphericalCoordinate(_Aligned):
     """The reference's ``MetricSphericalCoordinate`` on the GPU: ``project(mol)`` -> float32 ``[numFrames, 3]``: r, theta, phi of the
     vector from the centroid of ``refcom`` to the centroid of ``targetcom`` after aligning every frame on ``refmol``."""
 
-    def __init__(self, refmol, targetcom, refcom, trajalnsel="protein and name CA", refalnsel=None, centersel="protein", pbc=True):
+    def __init__(self, refmol, targetcom, refcom, trajalnsel="protein and name CA", refalnsel=None, centersel="protein", pbc=True,
+                 wrap_on_device=False):
         self._targetcom = targetcom
         self._refcom = refcom
-        self._init_align(refmol, trajalnsel, refalnsel, centersel, pbc)
+        self._init_align(refmol, trajalnsel, refalnsel, centersel, pbc, wrap_on_device)
 
     def _coms(self, mol):
         return (np.flatnonzero(_sel(mol, self._targetcom, "targetcom", "Atom selection for `targetcom` resulted in 0 atoms.")),
                 np.flatnonzero(_sel(mol, self._refcom, "refcom", "Atom selection for `refcom` resulted in 0 atoms.")))
 
     def project(self, mol, ctx=None):
-        _check_pbc(mol, self._pbc)
+        _check_pbc(mol, self._pbc and not self._wrap_on_device)
         target, ref = self._coms(mol)
-        return group_moments(mol.coords, [target, ref], align=self._align(mol), out="spherical", ctx=ctx)
+        w = self._wrapped(mol, np.concatenate([target, ref]), ctx)
+        if w is None:
+            return group_moments(mol.coords, [target, ref], align=self._align(mol), out="spherical", ctx=ctx)
+        return group_moments_trajectory(w.xyz, w.csr([target, ref]), affine=self._affine(mol, w), out="spherical", ctx=w.ctx).cpu().numpy()
 
     def getMapping(self, mol):
         target, ref = self._coms(mol)
@@ -508,7 +602,8 @@ class MetricSphericalCoordinate(_Aligned):
 # moleculekit hook
 # ------------------------------------------------------------------------------------------------
 def _ref_prepare(self, mol, centersel):
-    """the reference's own preamble of ``project``: a copy, wrapped on the host by the reference's ``Molecule.wrap`` where ``_pbc``"""
+    """the reference's own preamble of ``project``: a copy, wrapped by its ``Molecule.wrap`` where ``_pbc`` (on the device once
+    ``wrap.install()`` has swapped that method)"""
     mol = mol.copy()
     if self._pbc:
         mol.wrap(centersel)
@@ -615,7 +710,7 @@ def _targets():
 
 def install():
     """Swap ``project`` of an installed moleculekit's ``MetricCoordinate``, ``MetricGyration``, ``MetricFluctuation`` and
-    ``MetricSphericalCoordinate`` for the GPU's: wrapping stays the reference's own ``Molecule.wrap`` on the host, selections come
+    ``MetricSphericalCoordinate`` for the GPU's: wrapping is the molecule's own ``Molecule.wrap`` (the reference's on the host; the device's once ``wrap.install()`` has swapped it), selections come
     from the object's own ``_getMolProp``, alignment and moments run on the device.  Returns the originals; idempotent;
     ``uninstall()`` puts them back.  Independent of the other ``install()`` hooks."""
     saved = []
