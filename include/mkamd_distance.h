@@ -124,7 +124,9 @@ int mkamd_ctx_set_reduction_block(mkamd_ctx* ctx, int block);
  * "mkamd::k_sel_to_frames + mkamd::k_dist_rows<true, 4, true>"; empty before the first call): what bench.py reports as
  * the distance leg's `roofline.kernel` -- the choice depends on the shape of the call.  The shell, dihedral, moment and alignment
  * calls note theirs the same way (alignment: "mkamd::k_align_sums<AL_MATCH> G=64 segs=16 + mkamd::k_align_fold<17, 24>" -- the
- * sums' mode, the lanes per frame, and the fold exactly when the frames' selection was cut into segments). */
+ * sums' mode, the lanes per frame, and the fold exactly when the frames' selection was cut into segments), and so do the
+ * explicit-centre occupancy calls of mkamd_voxel.h ("mkamd::k_occupancy_centers, 8 waves": the workgroup width -- 4, 8 or 16 waves --
+ * that the number of centres and channels chose). */
 int mkamd_ctx_last_dist_kernel(mkamd_ctx* ctx, char* name, size_t name_cap);
 
 /* cdist(coords1 [n1,D], coords2 [n2,D]) -> results [n1,n2];  pdist(coords [n,D]) -> results [n(n-1)/2] */

@@ -197,7 +197,12 @@ int mkamd_calculate_occupancy_cpu_threads(const double* centers, int64_t n_cente
                                           const double* sigmas, int32_t n_channels, double* results, int32_t n_threads);
 
 /* (2) explicit (arbitrary) centres, float32 output, optional orthorhombic box (double[3], A;
- * NULL = not periodic).  sigmas_are_f64: 1 -> const double*, 0 -> const float*. */
+ * NULL = not periodic).  sigmas_are_f64: 1 -> const double*, 0 -> const float*.  Pair distances in double with one rounding
+ * per operation (never a fused multiply-add), so the strict d^2 < 25 decides as the reference's does to the last bit.  At most
+ * 524 280 channels (65 535 groups of eight: the launch grid's y) and at most 2^31 - 1 blocks of 64 centres (137 438 953 408
+ * centres: the grid's x) -- more of either comes back as MKAMD_EINVAL before anything is launched.  `_dev`: device pointers,
+ * launched on the context's stream without a synchronisation; n_centers = 0 touches nothing, n_atoms = 0 needs neither coords
+ * nor sigmas and writes zeros. */
 int mkamd_occupancy_centers_host(mkamd_ctx* ctx, const double* centers, int64_t n_centers,
                                  const float* coords, int64_t n_atoms, const void* sigmas,
                                  int sigmas_are_f64, int32_t n_channels, const double* box,

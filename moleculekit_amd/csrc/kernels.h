@@ -3268,6 +3268,8 @@ MK_KERNEL(64) void k_zero_words(unsigned* __restrict__ p, unsigned n)
 // Explicit (non-lattice) centres: the exact calculate_occupancy contract for arbitrary `centers`
 // (usercenters / direct calls).  Distances in DOUBLE exactly as the reference (float32 coords
 // promoted, strict d^2 < 25), min-q reduction in float32.  Brute force O(N*V).
+// "Exactly" needs one rounding per operation: the minimum image and d^2 are NEVER contracted into fused multiply-adds (the
+// pragma in the pair loop -- keep it: with v_fma_f64 a pair ON the 5 A shell came out inside, tests/centers_cases.py cutoff_case).
 // A workgroup owns 64 centres (lane = centre) and its waves split the ATOMS: the atoms go through LDS in chunks of one
 // atom per thread, wave w tests the w-th 64 of a chunk, and the waves' running minima meet in LDS (ds_min_u32 on the
 // bit patterns: order-free, so the result does not depend on the split) before the epilogue.  The host picks 4, 8 or 16
@@ -3312,6 +3314,11 @@ MK_KERNEL(EXPL_MAX_WAVES * WAVE) void k_occupancy_centers(const double* __restri
         const long long left = N - a0 - (long long)wv * WAVE;             // this wave's atoms of the chunk
         const int cnt = left < 0 ? 0 : (left < WAVE ? (int)left : WAVE);
         for (int k = 0; k < cnt; ++k) {
+            // one rounding per operation, as the reference: contracted into v_fma_f64 the sum of squares is rounded once, and a
+            // centre at (3 - 1 ulp, 4, 0) from an atom -- d^2 = 25 summed the reference's way -- came out inside the cut-off
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
             const int i = wv * WAVE + k;
             const float4 p = s_pos[i];
             double dx = (double)p.x - cx, dy = (double)p.y - cy, dz = (double)p.z - cz;

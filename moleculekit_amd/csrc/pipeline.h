@@ -786,6 +786,9 @@ int run_centers(BE& be, const double* d_centers, long long V, const float* d_coo
     if (box_host)
         for (int ax = 0; ax < 3; ++ax)
             if (!(box_host[ax] > 2.0 * CUTOFF_A)) { err = "periodic box edges must be > 10 A (2 x cutoff)"; return ST_EBOX; }
+    // the launch below is dim3(ceil(V / 64), G): refused here, by name, instead of by the runtime at the launch
+    if (((long long)C + CHG - 1) / CHG > 65535) { err = "explicit centres: at most 524280 channels (65535 channel groups of 8, the grid's y limit)"; return ST_EINVAL; }
+    if ((V - 1) / EXPL_CENTERS + 1 > 0x7fffffffLL) { err = "explicit centres: at most 2^31 - 1 blocks of 64 centres (the grid's x limit)"; return ST_EINVAL; }
     const int G = ceil_div(C, CHG);
     float4* w = nullptr;
     int st = ensure_as(be, WS_W_EXPLICIT, (size_t)(N > 0 ? N : 1) * sizeof(float4) * 2 * G, w, 0);
@@ -801,6 +804,7 @@ int run_centers(BE& be, const double* d_centers, long long V, const float* d_coo
     int waves = 4;
     while (waves < EXPL_MAX_WAVES && wgs * waves < 4096) waves *= 2;
     const dim3 grid((unsigned)ceil_div(V, EXPL_CENTERS), (unsigned)G), blk((unsigned)(waves * WAVE));
+    be.note_dist_kernel(("mkamd::k_occupancy_centers, " + std::to_string(waves) + " waves").c_str());   // (the tests: every block size runs)
     return be.launch(k_occupancy_centers, grid, blk, d_centers, V, d_coords, N, w, C,
                      box_host ? 1 : 0, box_host ? box_host[0] : 0.0, box_host ? box_host[1] : 0.0,
                      box_host ? box_host[2] : 0.0, d_out);
