@@ -307,6 +307,34 @@ int mkamd_wrap_box_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, in
                         int64_t n_rows, const uint32_t* starts, int64_t n_groups, const uint32_t* centersel, int64_t n_centersel,
                         const float* center, float* out);
 
+/* ---- periodic wrap of TRICLINIC boxes: the three unit cells of Molecule.wrap when a box angle is not 90 (moleculekit
+ * wrapping/wrapping.pyx wrap_compact_unitcell with mode 0 "rectangular" and mode 1 "compact", wrap_triclinic_unitcell: mode 2) ----
+ * Everything as for mkamd_wrap_box_dev / _host but the box: d_boxvectors float64 [3, 3, n_frames], row i the box vector i, lower
+ * triangular (box[0][1] = box[0][2] = box[1][2] = 0).  Every atom of a frame is first recentred, xc = (x - centre) + box_middle in
+ * float32 (box_middle[j] = float(double(box_middle[j]) + 0.5 box[i][j])); group centres are the float32 running means over xc.
+ * mode 2: the group's centre is moved by whole box vectors, for m = 2, 1, 0, until its fractional coordinate m lies in [0, 1) (GROMACS'
+ * put_atoms_in_triclinic_unitcell: float64 shifts, the float32 centre rounded after every step); atoms get x_m = xc_m - (centre before -
+ * centre after).  mode 0, 1: dx = double(group centre - box_middle) is brought into (-box[i][i] / 2, box[i][i] / 2] per axis by the
+ * diagonal (mode 0) or by whole box vectors followed by the search over the frame's up to 12 triclinic vectors (mode 1: GROMACS'
+ * pbc_dx); atoms get float(double((xc - group centre) + box_middle) + dx).  Each operation is rounded on its own: the results are the
+ * reference's bits.  Every atom is written, in place (d_out == d_xyz) as out of place.
+ * Where the reference's loops would not end, these do: each stops after mkamd_wrap_cell_max_steps() steps (one box vector a step)
+ * and the group is written with what was reached; a frame with a non-finite box vector, box[1][1] or box[2][2] not positive or a
+ * non-zero upper triangle is copied through unchanged.  d_status int [3] (or NULL) is cleared by the call and then holds 1 in
+ * [0] where a loop reached that cap, [1] where a frame was copied through, [2] where a frame has more than 12 triclinic vectors (it is
+ * copied through as well; the reference raises "Too many triclinic vectors!!").  The host form refuses such box vectors before it
+ * launches anything and returns MKAMD_EINVAL, with a message that names the condition, where a status word is set (out is filled).
+ * MKAMD_EINVAL besides: a mode other than 0, 1, 2, and everything mkamd_wrap_box_dev / _host refuse. */
+int64_t mkamd_wrap_cell_max_steps(void);
+/* asynchronous on the context's stream */
+int mkamd_wrap_cell_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t n_atoms, int64_t n_frames, const double* d_boxvectors,
+                        const uint32_t* d_starts, int64_t n_groups, const uint32_t* d_large, int64_t n_large, const uint32_t* d_centersel,
+                        int64_t n_centersel, const float* center, int mode, float* d_out, int* d_status);
+/* host arrays as for mkamd_wrap_box_host; boxvectors float64 [3, 3, n_frames].  Returns when out is filled. */
+int mkamd_wrap_cell_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const double* boxvectors,
+                         const uint32_t* rows, int64_t n_rows, const uint32_t* starts, int64_t n_groups, const uint32_t* centersel,
+                         int64_t n_centersel, const float* center, int mode, float* out);
+
 #ifdef __cplusplus
 }
 #endif

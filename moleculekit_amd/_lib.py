@@ -140,6 +140,9 @@ SIGNATURES = {
     "mkamd_wrap_small_max": (_c_i64, [_vp]),
     "mkamd_wrap_box_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
     "mkamd_wrap_box_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
+    "mkamd_wrap_cell_max_steps": (_c_i64, []),
+    "mkamd_wrap_cell_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _vp, _vp]),
+    "mkamd_wrap_cell_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _vp]),
 }
 
 _lib = None

@@ -15,6 +15,7 @@
 #include "dihedral_pipeline.h"
 #include "moments_pipeline.h"
 #include "wrap_pipeline.h"
+#include "wrap_cell_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "xtc_headers.h"
@@ -131,7 +132,7 @@ struct mkamd_ctx {
     void note_tail_reports(bool yes) { tail_reports = yes; }
     int dist_avoid = 0;                    // kernels dist_trajectory must not take (mkamd_ctx_set_dist_kernels: tests, A-B timing)
     int reduction_block = 0;               // k_dist_reduction_closest's first-group atoms in registers (mkamd_ctx_set_reduction_block)
-    char last_dist_kernel[96] = "";        // what the last dist_trajectory call launched (mkamd_ctx_last_dist_kernel)
+    char last_dist_kernel[128] = "";       // what the last dist_trajectory call launched (mkamd_ctx_last_dist_kernel)
     void note_dist_kernel(const char* name) { snprintf(last_dist_kernel, sizeof last_dist_kernel, "%s", name); }
     void note_dist_kernel_append(const char* more) { strncat(last_dist_kernel, more, sizeof last_dist_kernel - strlen(last_dist_kernel) - 1); }
     bool tail_reports = false;             // the last lattice call's k_tail writes FB_TILES_DONE / FB_TAIL_WROTE with seq_next
@@ -2459,6 +2460,79 @@ try {
     if ((st = ctx->ensure(WS_A_SLAB, bytes, &dslab))) return st;
     if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dxyz, F, 3 * M, 3 * M, 1.0f, (float*)dslab))) return st;
     return download(ctx, out, dslab, bytes, true);
+} MK_API_CATCH
+
+// ... of triclinic boxes (wrap_cell_pipeline.h)
+extern "C" int64_t mkamd_wrap_cell_max_steps(void) { return (int64_t)mkamd::WRAP_CELL_MAX_STEPS; }
+
+extern "C" int mkamd_wrap_cell_dev(mkamd_ctx* ctx, const float* d_xyz, int64_t N, int64_t F, const double* d_boxvectors, const uint32_t* d_starts,
+                                   int64_t G, const uint32_t* d_large, int64_t n_large, const uint32_t* d_centersel, int64_t n_c,
+                                   const float* center, int mode, float* d_out, int* d_status)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (n_c == 0 && !center && N > 0 && F > 0 && G > 0) return fail(MKAMD_EINVAL, "NULL pointer (neither a centre selection nor a centre)");
+    mkamd::WrapCellArgs c;
+    mkamd::WrapArgs& a = c.w;
+    a.xyz = d_xyz; a.n_atoms = N; a.n_frames = F; a.starts = d_starts; a.n_groups = G; a.large = d_large; a.n_large = n_large;
+    a.centersel = d_centersel; a.n_centersel = n_c; a.out = d_out;
+    if (n_c == 0 && center) { a.center[0] = center[0]; a.center[1] = center[1]; a.center[2] = center[2]; }
+    c.boxvectors = d_boxvectors; c.mode = mode; c.status = d_status;
+    if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0, mkamd::WRAP_CELL_NSTATUS * sizeof(int), ctx->stream));
+    std::string err;
+    st = mkamd::run_wrap_cell(*ctx, c, err, (ctx->dist_avoid >> 14) & 3);
+    return run_status(st, err);
+} MK_API_CATCH
+
+extern "C" int mkamd_wrap_cell_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const double* boxvectors, const uint32_t* rows,
+                                    int64_t n_rows, const uint32_t* starts, int64_t G, const uint32_t* centersel, int64_t n_c,
+                                    const float* center, int mode, float* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (mode < 0 || mode > 2) return fail(MKAMD_EINVAL, "mode must be 0 (rectangular), 1 (compact) or 2 (triclinic)");
+    if (N < 0 || F < 0 || G < 0 || n_c < 0 || n_rows < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (N > 0x3fffffffLL || F > 0x3fffffffLL) return fail(MKAMD_EINVAL, "too many atoms or frames (>= 2^30)");
+    const int64_t M = rows ? n_rows : N;                             // atoms that travel
+    if (F == 0 || M == 0) return MKAMD_OK;
+    if (!coords || !boxvectors || !out || (n_c > 0 && !centersel) || (n_c == 0 && !center)) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (const char* e = mkamd::wrap_cell_check_boxvectors(boxvectors, F)) return fail(MKAMD_EINVAL, e);
+    if (rows) {
+        if ((st = check_indices(rows, n_rows, N, "rows: atom"))) return st;
+        for (int64_t k = 1; k < n_rows; ++k)
+            if (rows[k] <= rows[k - 1]) return fail(MKAMD_EINVAL, "rows must be strictly increasing atom indices");
+    }
+    if (const char* e = mkamd::wrap_check_starts(starts, G, M)) return fail(MKAMD_EINVAL, e);
+    if ((st = check_indices(centersel, n_c, N, "centersel: atom"))) return st;
+    if (rows)
+        for (int64_t k = 0; k < n_c; ++k)
+            if (!std::binary_search(rows, rows + n_rows, centersel[k])) return fail(MKAMD_EINVAL, "centersel names an atom that is not among the rows");
+    HostStage up(ctx, coords, N, F, {{rows, n_rows}}, /*always=*/rows != nullptr);
+    void *dxyz, *dslab, *dbox, *dstarts, *dstatus, *dlarge = nullptr, *dsel = nullptr;
+    if ((st = upload_frame_major(ctx, WS_A_SLAB, WS_A_XYZ, up.host_rows(), 3 * M, F, &dxyz))) return st;
+    const int64_t small_max = mkamd_wrap_small_max(ctx);
+    std::vector<uint32_t> large;
+    for (int64_t g = 0; g < G; ++g)
+        if ((int64_t)starts[g + 1] - (int64_t)starts[g] > small_max) large.push_back((uint32_t)g);
+    if ((st = upload(ctx, WS_W_STARTS, starts, (size_t)(G + 1) * 4, &dstarts))) return st;
+    if (!large.empty() && (st = upload(ctx, WS_W_LARGE, large.data(), large.size() * 4, &dlarge))) return st;
+    if (n_c > 0 && (st = up.list_to(WS_W_SEL, centersel, n_c, &dsel))) return st;
+    if ((st = upload(ctx, WS_W_BOXV, boxvectors, (size_t)9 * F * 8, &dbox))) return st;
+    if ((st = ctx->ensure(WS_W_STATUS, mkamd::WRAP_CELL_NSTATUS * sizeof(int), &dstatus))) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));                      // (`large`, the packed rows and the rewritten selection are read by then)
+    up.held.clear();
+    st = mkamd_wrap_cell_dev(ctx, (const float*)dxyz, M, F, (const double*)dbox, (const uint32_t*)dstarts, G, (const uint32_t*)dlarge,
+                             (int64_t)large.size(), (const uint32_t*)dsel, n_c, center, mode, (float*)dxyz, (int*)dstatus);
+    if (st) return st;
+    // back to the reference's [M][3][F]
+    const size_t bytes = (size_t)3 * M * F * 4;
+    if ((st = ctx->ensure(WS_A_SLAB, bytes, &dslab))) return st;
+    if ((st = mkamd_frames_to_items_dev(ctx, ctx->stream, (const float*)dxyz, F, 3 * M, 3 * M, 1.0f, (float*)dslab))) return st;
+    if ((st = download(ctx, out, dslab, bytes, true))) return st;
+    int status[mkamd::WRAP_CELL_NSTATUS];
+    if ((st = download(ctx, status, dstatus, sizeof status, false))) return st;
+    if (const char* e = mkamd::wrap_cell_status_error(status)) return fail(MKAMD_EINVAL, e);
+    return MKAMD_OK;
 } MK_API_CATCH
 
 #ifdef MK_PHASE_TIMERS

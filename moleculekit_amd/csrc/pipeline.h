@@ -48,6 +48,8 @@ enum WsSlot {
     WS_M_PART, WS_M_REF, WS_M_ATOMS, WS_M_OFFS, WS_M_W, WS_M_REFIN,
     // periodic wrap (wrap_pipeline.h) and its host entry point
     WS_W_CENTRE, WS_W_STARTS, WS_W_LARGE, WS_W_SEL,
+    // ... of triclinic boxes (wrap_cell_pipeline.h): the frames' records; the host entry point's box vectors and status words
+    WS_W_CELL, WS_W_BOXV, WS_W_STATUS,
     WS_NSLOTS
 };
 

@@ -3,12 +3,16 @@
 The reference's ``Molecule.wrap`` moves every bonded group of every frame by whole box lengths back to within half a box of a centre
 -- the first step of every projection it offers (``mol.wrap(centersel)``, then ``mol.align(...)``) -- in a serial loop on the host.
 Here the same arithmetic, to the bit, runs on the device (csrc/wrap_kernels.h): the centres are float32 running means in atom
-order, so a group on the cell's boundary lands where the reference puts it.  The rectangular cell only; triclinic cells are refused
-(or, once ``install()``-ed, handed back to the reference).
+order, so a group on the cell's boundary lands where the reference puts it.  Rectangular boxes take ``wrap_box``'s kernels; triclinic
+boxes (a box angle other than 90) take the reference's three unit cells -- "rectangular", "compact", "triclinic" -- through
+csrc/wrap_cell_kernels.h, opted into with ``wrap_molecule(..., triclinic_on_device=True)`` or ``install(triclinic=True)``.
 
 * ``bonded_groups(bonds, n_atoms)`` -- the starts of the bonded groups (the reference's ``getBondedGroups``), on the host.
 * ``wrap_trajectory`` -- CUDA tensors, frame-major ``[F, N, 3]`` float32 and a ``[3, F]`` box; asynchronous; in place or not.
 * ``wrap`` -- numpy arrays ``[N, 3, F]`` through the host entry point (``rows``: only the atoms that matter travel).
+* ``box_vectors`` -- box lengths and angles to the float64 box vectors ``[3, 3, F]`` (the reference's ``Molecule.boxvectors``).
+* ``wrap_cell_trajectory`` / ``wrap_cell`` -- the same two forms for triclinic boxes: box vectors and a unit cell.  Where the reference's
+  loops would not end (an infinite coordinate, a degenerate box) these stop after ``WRAP_CELL_MAX_STEPS`` steps and raise.
 * ``wrap_molecule`` -- ``Molecule.wrap`` on a molecule-like object; ``install()`` / ``uninstall()`` swap ``Molecule.wrap`` of an
   installed moleculekit.
 
@@ -27,6 +31,16 @@ logger = logging.getLogger(__name__)
 
 _F32, _U32 = np.float32, np.uint32
 UNITCELLS = ("rectangular", "triclinic", "compact")
+_F64 = np.float64
+CELL_MODES = {"rectangular": 0, "compact": 1, "triclinic": 2}    # csrc/wrap_cell_kernels.h: WRAP_CELL_*
+WRAP_CELL_MAX_STEPS = 4096                                        # ... WRAP_CELL_MAX_STEPS (mkamd_wrap_cell_max_steps)
+_STATUS_ERRORS = (                                                # ... WRAP_CELL_ST_*, in the order they are reported
+    (2, "Too many triclinic vectors!!"),
+    (1, "wrap: a frame's box vectors are degenerate (non-finite, box[1][1] or box[2][2] not positive, or not lower triangular); the frame "
+        "was copied through unchanged"),
+    (0, f"wrap: a group did not come into the cell within {WRAP_CELL_MAX_STEPS} steps (an infinite coordinate, or a box length far below "
+        "the coordinates); it was written with what was reached"),
+)
 
 
 class NonContiguousGroups(ValueError):
@@ -247,6 +261,181 @@ def wrap(coords, box, groups_or_bonds, centersel=None, center=None, rows=None, c
 
 
 # ------------------------------------------------------------------------------------------------
+# triclinic boxes
+# ------------------------------------------------------------------------------------------------
+def box_vectors(box, boxangles):
+    """The box vectors of every frame, float64 ``[3, 3, F]`` (row i: vector i; lower triangular), from the box lengths ``[3, F]`` and the
+    angles ``[3, F]`` (alpha, beta, gamma in degrees) -- the reference's ``Molecule.boxvectors``: float64 throughout, its order of
+    operations, components within 1e-6 of zero set to 0.  All zeros when lengths and angles are all zero; ``AssertionError`` when an
+    angle is 0."""
+    b, ang = np.asarray(box), np.asarray(boxangles)
+    if b.ndim == 1:
+        b = b[:, None]
+    if ang.ndim == 1:
+        ang = ang[:, None]
+    if b.ndim != 2 or b.shape[0] != 3 or ang.shape != b.shape:
+        raise ValueError(f"box and boxangles must both have shape (3, frames), got {b.shape} and {ang.shape}")
+    F = b.shape[1]
+    if np.all(ang == 0) and np.all(b == 0):
+        return np.zeros((3, 3, F), _F64)
+    assert np.all(ang != 0), "Box angles should not be 0"
+    a_len, b_len, c_len = (b[i].astype(_F64) for i in range(3))
+    alpha, beta, gamma = (ang[i].astype(_F64) * np.pi / 180 for i in range(3))
+    out = np.zeros((3, 3, F), _F64)
+    out[0, 0] = a_len
+    out[1, 0] = b_len * np.cos(gamma)
+    out[1, 1] = b_len * np.sin(gamma)
+    cx = c_len * np.cos(beta)
+    cy = c_len * (np.cos(alpha) - np.cos(beta) * np.cos(gamma)) / np.sin(gamma)
+    with np.errstate(invalid="ignore"):
+        cz = np.sqrt(c_len * c_len - cx * cx - cy * cy)
+    out[2, 0], out[2, 1], out[2, 2] = cx, cy, cz
+    tol = 1e-6
+    out[np.logical_and(out > -tol, out < tol)] = 0.0
+    return out
+
+
+def _check_boxvectors(bv):
+    """what the library checks before it launches (csrc/wrap_cell_pipeline.h: wrap_cell_check_boxvectors), on a host array [3, 3, F]"""
+    if not np.all(np.isfinite(bv)):
+        raise ValueError("box vectors: a component is not finite")
+    if not (np.all(bv[1, 1] > 0) and np.all(bv[2, 2] > 0)):
+        raise ValueError("box vectors: box[1][1] and box[2][2] must be positive")
+    if np.any(bv[0, 1] != 0) or np.any(bv[0, 2] != 0) or np.any(bv[1, 2] != 0):
+        raise ValueError("box vectors: not lower triangular (box[0][1], box[0][2], box[1][2] must be 0)")
+
+
+def _host_boxvectors(boxvectors, F):
+    bv = np.asarray(boxvectors)
+    if bv.ndim == 2:
+        bv = bv[:, :, None]
+    if bv.shape != (3, 3, F):
+        raise ValueError(f"boxvectors must have shape (3, 3, {F}), got {bv.shape}")
+    return np.array(bv, dtype=_F64, order="C")                 # (a copy: 72 B a frame, and the caller's array may be read-only)
+
+
+def _cell_mode(unitcell):
+    if not isinstance(unitcell, str) or unitcell.lower() not in CELL_MODES:
+        raise ValueError(f"Invalid unit cell type: {unitcell}. Must be one of: rectangular, triclinic, compact")
+    return CELL_MODES[unitcell.lower()]
+
+
+def status_error(status):
+    """the message of the first condition set in the three status words of a cell wrap, or None"""
+    st = [int(v) for v in np.asarray(status).reshape(-1)[:3]]
+    for word, text in _STATUS_ERRORS:
+        if st[word]:
+            return text
+    return None
+
+
+def wrap_cell_trajectory(xyz, boxvectors, groups, unitcell, *, centersel=None, center=None, out=None, stream=None, ctx=None, check=True):
+    """Wrap every frame of a device-resident trajectory into a unit cell of its triclinic box.  ``xyz``: CUDA float32 ``[F, N, 3]``;
+    ``boxvectors``: float64 ``[3, 3, F]`` (``box_vectors``; an array or a CUDA tensor); ``groups``, ``centersel`` / ``center``, ``out`` and
+    ``stream`` as in ``wrap_trajectory``; ``unitcell``: "rectangular", "compact" or "triclinic" -- the reference's three modes of
+    ``Molecule.wrap`` for a box whose angles are not all 90.  Every atom is written (each frame is recentred first), in place as well.
+    The box vectors are checked before anything is launched (an array always; a CUDA tensor when ``check``): ``ValueError``.
+    ``check=True``: the call synchronises, reads the status words and raises ``ValueError`` where the reference's loops would not have
+    ended (a group that did not come into the cell within ``WRAP_CELL_MAX_STEPS`` steps), a frame was degenerate or had more than 12
+    triclinic vectors; it returns the wrapped tensor.  ``check=False``: asynchronous; returns ``(tensor, status)`` with ``status`` a CUDA
+    int32 tensor of three words (``status_error``).  The bits are the reference's ``wrap_triclinic_unitcell`` / ``wrap_compact_unitcell``."""
+    import torch
+
+    from .moments import _device_inputs
+
+    mode = _cell_mode(unitcell)
+    inplace = out is xyz
+    if inplace and not (hasattr(xyz, "is_contiguous") and xyz.is_contiguous() and xyz.dim() == 3):
+        raise ValueError("in place needs a contiguous [frames, atoms, 3] tensor")
+    src, _, dev, ctx = _device_inputs(xyz, None, stream, ctx)
+    F, N = int(src.shape[0]), int(src.shape[1])
+    starts = _starts(groups, N)
+    sel, cen = _centre_inputs(centersel, center, N)
+    if hasattr(boxvectors, "is_cuda"):
+        if boxvectors.dtype != torch.float64 or tuple(boxvectors.shape) != (3, 3, F):
+            raise ValueError(f"boxvectors must be float64 [3, 3, {F}], got {boxvectors.dtype} {tuple(boxvectors.shape)}")
+        if check:
+            _check_boxvectors(boxvectors.detach().cpu().numpy())
+        d_bv = boxvectors.to(dev).contiguous()
+    else:
+        bv = _host_boxvectors(boxvectors, F)
+        _check_boxvectors(bv)
+        d_bv = torch.as_tensor(bv, device=dev)
+    if inplace:
+        res = src
+    elif out is None:
+        res = torch.empty_like(src)
+    else:
+        if not (hasattr(out, "is_cuda") and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == src.shape
+                and out.device == src.device):
+            raise ValueError("out must be a contiguous float32 CUDA tensor shaped like xyz, on its device")
+        if out.data_ptr() == src.data_ptr():
+            raise ValueError("out shares xyz's memory: pass out=xyz for an in-place wrap")
+        res = out
+    status = torch.zeros(3, dtype=torch.int32, device=dev)
+    if F == 0 or N == 0:
+        return res if check else (res, status)
+    large = _large(starts, ctx)
+    d_starts = torch.as_tensor(starts.view(np.int32), device=dev)
+    d_large = torch.as_tensor(large.view(np.int32), device=dev) if large.size else None
+    d_sel = torch.as_tensor(sel.view(np.int32), device=dev) if sel is not None else None
+    if stream is not None:
+        torch.cuda.current_stream(dev).synchronize()           # (status and a conversion of the box vectors ran on torch's stream)
+    _lib._check(_lib.load().mkamd_wrap_cell_dev(ctx._h, src.data_ptr(), N, F, d_bv.data_ptr(), d_starts.data_ptr(), int(starts.size) - 1,
+                                                d_large.data_ptr() if d_large is not None else None, int(large.size),
+                                                d_sel.data_ptr() if d_sel is not None else None, 0 if sel is None else int(sel.size),
+                                                _lib._ptr(cen), mode, res.data_ptr(), status.data_ptr()))
+    if stream is not None:
+        ctx.synchronize()          # (the index tensors are torch's: their memory must not be reused before a foreign stream has read it)
+    if not check:
+        return res, status
+    ctx.synchronize()
+    message = status_error(status.cpu().numpy())
+    if message:
+        raise ValueError(message)
+    return res
+
+
+def wrap_cell(coords, boxvectors, groups_or_bonds, unitcell, centersel=None, center=None, rows=None, ctx=None):
+    """``wrap_cell_trajectory`` on host arrays in the reference's layout: ``coords`` float32 ``[N, 3, F]``, ``boxvectors`` float64
+    ``[3, 3, F]``; ``groups_or_bonds`` and ``rows`` as in ``wrap``.  Returns a wrapped copy (of the rows named, with ``rows``).  The box
+    vectors are checked first; a status word set by the run raises ``ValueError`` with the condition's name."""
+    mode = _cell_mode(unitcell)
+    coords = _coords(coords)
+    N, _, F = coords.shape
+    bv = _host_boxvectors(boxvectors, F)
+    _check_boxvectors(bv)
+    starts = _groups_or_bonds(groups_or_bonds, N)
+    sel, cen = _centre_inputs(centersel, center, N)
+
+    def run(travel, n_travel, packed, out):
+        h = (ctx or _lib.default_context())._h                  # (a status word set by the run comes back as MKAMD_EINVAL: ValueError)
+        _lib._check(_lib.load().mkamd_wrap_cell_host(h, _lib._ptr(coords), N, F, _lib._ptr(bv), _lib._ptr(travel), n_travel, _lib._ptr(packed),
+                                                     int(packed.size) - 1, _lib._ptr(sel), 0 if sel is None else int(sel.size),
+                                                     _lib._ptr(cen), mode, _lib._ptr(out)))
+
+    if rows is None:
+        out = np.empty_like(coords)
+        if N == 0 or F == 0:
+            return out
+        run(None, 0, starts, out)
+        return out
+    r = _np(rows)
+    if r.dtype == bool:
+        named = np.flatnonzero(_mask(r, N, "rows"))
+    else:
+        _mask(r, N, "rows")                                     # (the checks: integers, in range)
+        named = r.astype(np.int64).reshape(-1)
+        named = np.where(named < 0, named + N, named)
+    if named.size == 0 or F == 0:
+        return np.empty((int(named.size), 3, F), _F32)
+    travel, packed = travel_rows(starts, named, sel)
+    out = np.empty((int(travel.size), 3, F), _F32)
+    run(travel, int(travel.size), packed, out)
+    return np.ascontiguousarray(out[np.searchsorted(travel, named)])
+
+
+# ------------------------------------------------------------------------------------------------
 # Molecule.wrap
 # ------------------------------------------------------------------------------------------------
 _ZERO_BOX = ("Zero box size detected in `Molecule.box`; skipping wrap. Read a topology / trajectory containing box information, "
@@ -272,13 +461,16 @@ def _select(mol, sel, N, guess_bonds):
     return np.where(a < 0, a + N, a).astype(_U32)
 
 
-def wrap_molecule(mol, wrapsel="all", fileBonds=True, guessBonds=False, wrapcenter=None, unitcell="rectangular", ctx=None):
-    """The reference's ``Molecule.wrap`` for rectangular cells, on the GPU: ``mol.coords`` (float32 ``[N, 3, F]``) is wrapped in place
-    around the atoms ``wrapsel`` (a mask or an index array; ``"all"``) or around ``wrapcenter``, by the bonded groups of ``mol.bonds``
+def wrap_molecule(mol, wrapsel="all", fileBonds=True, guessBonds=False, wrapcenter=None, unitcell="rectangular", ctx=None, *,
+                  triclinic_on_device=False):
+    """The reference's ``Molecule.wrap`` on the GPU: ``mol.coords`` (float32 ``[N, 3, F]``) is wrapped in place around the atoms
+    ``wrapsel`` (a mask or an index array; ``"all"``) or around ``wrapcenter``, by the bonded groups of ``mol.bonds``
     (``fileBonds=False``: every atom on its own).  As the reference: ``ValueError`` for an unknown ``unitcell``, a warning and no
     change when the whole box is zero, ``RuntimeError`` when box and coordinates differ in their number of frames.  Unlike it:
-    ``guessBonds=True`` and any ``boxangles`` other than 90 raise ``NotImplementedError`` -- the triclinic modes "rectangular",
-    "triclinic" and "compact" are not on the device --, a bonded group that is not contiguous raises ``ValueError``."""
+    ``guessBonds=True`` raises ``NotImplementedError``, a bonded group that is not contiguous raises ``ValueError``, and a triclinic
+    box (any ``boxangles`` other than 90 in any frame) raises ``NotImplementedError`` unless ``triclinic_on_device=True``: then, as in
+    the reference, the whole call takes ``wrap_cell`` with ``box_vectors(mol.box, mol.boxangles)`` and ``unitcell`` ("rectangular",
+    "triclinic" or "compact"); a box whose angles are all 90 takes ``wrap`` whatever ``unitcell`` says."""
     unitcell = unitcell.lower()
     if unitcell not in UNITCELLS:
         raise ValueError(f"Invalid unit cell type: {unitcell}. Must be one of: rectangular, triclinic, compact")
@@ -308,22 +500,28 @@ def wrap_molecule(mol, wrapsel="all", fileBonds=True, guessBonds=False, wrapcent
     if guessBonds:
         raise NotImplementedError("guessBonds=True: this package does not guess bonds; pass a molecule whose bonds are read from a topology")
     angles = getattr(mol, "boxangles", None)
-    if angles is not None and np.size(angles) and np.any(np.asarray(angles) != 90):
+    triclinic = angles is not None and np.size(angles) and bool(np.any(np.asarray(angles) != 90))
+    if triclinic and not triclinic_on_device:
         raise NotImplementedError("the box is triclinic (boxangles != 90): the unit cells 'rectangular', 'triclinic' and 'compact' of a "
                                   "triclinic box are not wrapped on the device; use the reference's Molecule.wrap")
     groups = bonded_groups(bonds if fileBonds else None, N)
+    if triclinic:
+        mol.coords[...] = wrap_cell(np.ascontiguousarray(coords, dtype=_F32), box_vectors(box, angles), groups, unitcell,
+                                    centersel=centersel if center is None else None, center=center, ctx=ctx)
+        return
     mol.coords[...] = wrap(np.ascontiguousarray(coords, dtype=_F32), box, groups, centersel=centersel if center is None else None, center=center,
                            ctx=ctx)
 
 
 def _molecule_wrap(self, wrapsel="all", fileBonds=True, guessBonds=False, wrapcenter=None, unitcell="rectangular"):
-    """``Molecule.wrap`` once ``install()``-ed: the device for rectangular cells; the saved original for triclinic boxes, guessed bonds
-    and bonded groups that are not contiguous"""
+    """``Molecule.wrap`` once ``install()``-ed: the device for rectangular boxes and, after ``install(triclinic=True)``, triclinic ones;
+    the saved original for guessed bonds, bonded groups that are not contiguous and (by default) triclinic boxes"""
     import moleculekit.molecule as ref
 
     original = ref._mkamd_reference_wrap
     angles = getattr(self, "boxangles", None)
-    triclinic = angles is not None and np.size(angles) and np.any(np.asarray(angles) != 90)
+    on_device = bool(getattr(ref, "_mkamd_wrap_triclinic", False))
+    triclinic = angles is not None and np.size(angles) and np.any(np.asarray(angles) != 90) and not on_device
     if guessBonds or triclinic or not isinstance(unitcell, str) or unitcell.lower() not in UNITCELLS:
         return original(self, wrapsel, fileBonds, guessBonds, wrapcenter, unitcell)
     try:
@@ -331,16 +529,18 @@ def _molecule_wrap(self, wrapsel="all", fileBonds=True, guessBonds=False, wrapce
             bonded_groups(self.bonds, int(np.asarray(self.coords).shape[0]))
     except NonContiguousGroups:
         return original(self, wrapsel, fileBonds, guessBonds, wrapcenter, unitcell)
-    return wrap_molecule(self, wrapsel, fileBonds, guessBonds, wrapcenter, unitcell)
+    return wrap_molecule(self, wrapsel, fileBonds, guessBonds, wrapcenter, unitcell, triclinic_on_device=on_device)
 
 
-def install():
+def install(triclinic=False):
     """Swap ``Molecule.wrap`` of an installed moleculekit for the GPU's: the reference's own projections (``mol.wrap(centersel)``,
-    then ``mol.align(...)``) and everything else built on ``Molecule.wrap`` then wrap on the device.  Triclinic boxes,
-    ``guessBonds=True`` and molecules whose bonded groups are not contiguous go to the saved original.  Returns the original;
-    idempotent; ``uninstall()`` puts it back.  Independent of the other ``install()`` hooks."""
+    then ``mol.align(...)``) and everything else built on ``Molecule.wrap`` then wrap on the device.  ``guessBonds=True`` and
+    molecules whose bonded groups are not contiguous go to the saved original, and so do triclinic boxes unless ``triclinic=True``
+    (the last call's value holds).  Returns the original; idempotent; ``uninstall()`` puts it back and clears the flag.  Independent of
+    the other ``install()`` hooks."""
     import moleculekit.molecule as ref
 
+    ref._mkamd_wrap_triclinic = bool(triclinic)
     saved = getattr(ref, "_mkamd_reference_wrap", None)
     if saved is not None:
         return saved
@@ -355,6 +555,7 @@ def uninstall():
     import moleculekit.molecule as ref
 
     saved = getattr(ref, "_mkamd_reference_wrap", None)
+    ref._mkamd_wrap_triclinic = False
     if saved is not None:
         ref.Molecule.wrap = saved
         ref._mkamd_reference_wrap = None
