@@ -335,6 +335,43 @@ int mkamd_wrap_cell_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, i
                          const uint32_t* rows, int64_t n_rows, const uint32_t* starts, int64_t n_groups, const uint32_t* centersel,
                          int64_t n_centersel, const float* center, int mode, float* out);
 
+/* ---- ring interactions: pi-pi stacking, cation-pi and sigma-hole contacts of every frame (moleculekit interactions/pipi/pipi.pyx,
+ * cationpi/cationpi.pyx, sigmahole/sigmahole.pyx: `calculate`) ----
+ * kind 0 pi-pi: every ring of list 1 against every ring of list 2; 1 cation-pi: every ring against every cation; 2 sigma-hole: every
+ * ring against every (halogen, bonded atom) pair.  The arguments are `calculate`'s:
+ *   ring_atoms uint32 [n_ring_atoms]   the rings' atoms, concatenated (pi-pi: both lists, as the reference's wrapper builds them)
+ *   starts1 uint32 [n1 + 1]            offsets of the rings of list 1 into ring_atoms; every ring has at least 3 atoms
+ *   starts2 uint32 [n2 + 1]            kind 0: the same for list 2 (NULL otherwise).  A pair of rings with the same (start, end) is
+ *                                      skipped, as in the reference -- whose wrapper shifts list 2 behind list 1, so that a ring named in
+ *                                      both lists DOES pair with itself
+ *   partners uint32 [n2] / [n2, 2]     kind 1: the cations; kind 2: (halogen, bonded atom) rows (NULL for kind 0)
+ *   thresholds float [4], host         kind 0: dist_threshold1, angle_threshold1_max, dist_threshold2, angle_threshold2_min; kinds 1, 2:
+ *                                      dist_threshold, angle_threshold_min (the other two are not read).  Distances are squared in float32
+ * box float32 [3, n_frames]: the minimum image is applied per axis only where |d| > box / 2 and box != 0 (a zero axis is open; there is
+ * no pbc flag); box NULL: every axis open.  Every float32 operation up to the squared distance and the dot product is the reference's,
+ * rounded on its own; the angle is acos in float64 times 57.29578, folded at 90 (kinds 1, 2: 90 minus it).  A NaN angle fails every
+ * comparison: the pair is dropped, as the reference drops it.
+ * Results, the reference's order (frame; ring of list 1; partner): frame_offsets int64 [n_frames + 1] (host); *pairs uint32 [2 n]: the
+ * ring's index in list 1 and the ring's index in list 2 (kind 0) / the cation's or halogen's ATOM index; *distang float32 [2 n]:
+ * distance and angle in degrees.  Both lists are context-owned (NULL when n = 0) and valid until the next ring call on the context.
+ * _dev: device pointers (coords [n_atoms, 3, n_frames]); the atom indices are NOT checked; the lists are device memory.  Not
+ * asynchronous: the counts reach the host to size the lists.  MKAMD_EINVAL: a kind other than 0, 1, 2; a ring of fewer than 3 atoms;
+ * offsets that decrease or leave ring_atoms; a NaN threshold; more than 2^30 pairs or frames. */
+int mkamd_ring_interactions_dev(mkamd_ctx* ctx, int kind, const float* d_coords, int64_t n_atoms, int64_t n_frames, const float* d_box,
+                                const uint32_t* d_ring_atoms, int64_t n_ring_atoms, const uint32_t* d_starts1, int64_t n1,
+                                const uint32_t* d_starts2, const uint32_t* d_partners, int64_t n2, const float* thresholds,
+                                int64_t* frame_offsets, const uint32_t** d_pairs, const float** d_distang);
+/* host arrays; every atom index is checked against n_atoms (MKAMD_EINVAL); only the rows of the rings' and partners' atoms are packed
+ * and uploaded (csrc/host_pack.h); the lists are host memory and name atoms of the caller's array. */
+int mkamd_ring_interactions_host(mkamd_ctx* ctx, int kind, const float* coords, int64_t n_atoms, int64_t n_frames, const float* box,
+                                 const uint32_t* ring_atoms, int64_t n_ring_atoms, const uint32_t* starts1, int64_t n1,
+                                 const uint32_t* starts2, const uint32_t* partners, int64_t n2, const float* thresholds,
+                                 int64_t* frame_offsets, const uint32_t** pairs, const float** distang);
+/* The launch plan of the ring calls (tests, same-box A-B timing).  avoid_mask: 1 not the kernels whose lanes run along frames, 2 not
+ * those whose lanes run along the pairs of one frame (default 0: by the shape of the call).  chunk_frames > 0: that many frames per
+ * chunk instead of what a 256 MB workspace allows (0: default).  Every plan produces the same lists. */
+int mkamd_ctx_set_ring_plan(mkamd_ctx* ctx, int avoid_mask, int64_t chunk_frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,12 @@ SIGNATURES = {
     "mkamd_wrap_cell_max_steps": (_c_i64, []),
     "mkamd_wrap_cell_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _vp, _vp]),
     "mkamd_wrap_cell_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _vp]),
+    # include/mkamd_distance.h, ring interactions
+    "mkamd_ring_interactions_dev": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp,
+                                             ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "mkamd_ring_interactions_host": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp,
+                                              ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "mkamd_ctx_set_ring_plan": (_c_int, [_vp, _c_int, _c_i64]),
 }
 
 _lib = None
@@ -383,6 +389,11 @@ class Context:
         of the selected atoms' rows); 64: selfdist calls keep the pair-table kernel (no triangular row kernel); 128: short-row calls of few frames keep the tile kernel (no swapped row kernel); 256 / 512: shell counts avoid their frame-lane / atom-lane kernel; 1024 / 2048: dihedrals the same; 4096 / 8192: group moments avoid the form in which a lane group owns a (frame, group) / the segmented form; 16384 / 32768: the periodic wrap avoids its lane-per-group / wave-per-group kernel; 0 = free choice.  Same bits whichever runs (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_dist_kernels(self._h, int(avoid_mask)))
 
+    def set_ring_plan(self, avoid_mask: int = 0, chunk_frames: int = 0):
+        """The launch plan of the ring-interaction calls (include/mkamd_distance.h): avoid 1 the frame-lane kernels, 2 the pair-lane
+        kernels; ``chunk_frames`` > 0 forces the frames per chunk.  Every plan produces the same lists (tests, A-B timing)."""
+        _check(load().mkamd_ctx_set_ring_plan(self._h, int(avoid_mask), int(chunk_frames)))
+
     def set_reduction_block(self, block: int = 0):
         """0: choose; 4 / 8: first-group atoms a wave of the closest-atom group reduction keeps in registers; -1: the generic kernel."""
         _check(load().mkamd_ctx_set_reduction_block(self._h, int(block)))
@@ -519,6 +530,31 @@ class Context:
         _check(load().mkamd_contacts_trajectory_dev(self._h, _ptr(d_coords), F, _ptr(d_box), _ptr(d_sel1), n1, _ptr(d_sel2), n2, _ptr(d_chains),
                                                     int(selfdist), int(pbc), float(threshold), _ptr(offs), ctypes.byref(ptr)))
         return offs, int(ptr.value or 0), int(offs[-1])
+
+    def ring_interactions_host(self, kind, coords, box, ring_atoms, starts1, starts2, partners, n2, thresholds):
+        """-> (frame_offsets int64 [F+1], pairs uint32 [n, 2], distang float32 [n, 2]) -- decided and compacted on the GPU."""
+        N, _, F = coords.shape
+        offs = np.zeros(F + 1, dtype=np.int64)
+        pp, pd = _vp(None), _vp(None)
+        _check(load().mkamd_ring_interactions_host(self._h, int(kind), _ptr(coords), N, F, _ptr(box), _ptr(ring_atoms), ring_atoms.shape[0],
+                                                   _ptr(starts1), starts1.shape[0] - 1, _ptr(starts2), _ptr(partners), int(n2), _ptr(thresholds),
+                                                   _ptr(offs), ctypes.byref(pp), ctypes.byref(pd)))
+        n = int(offs[-1])
+        if n == 0 or not pp.value or not pd.value:
+            return offs, np.zeros((0, 2), dtype=np.uint32), np.zeros((0, 2), dtype=np.float32)
+        pairs = np.frombuffer((ctypes.c_uint32 * (2 * n)).from_address(pp.value), dtype=np.uint32).reshape(n, 2).copy()   # context-owned: copied
+        distang = np.frombuffer((ctypes.c_float * (2 * n)).from_address(pd.value), dtype=np.float32).reshape(n, 2).copy()
+        return offs, pairs, distang
+
+    def ring_interactions_dev(self, kind, d_coords, N, F, d_box, d_ring_atoms, n_ring_atoms, d_starts1, n1, d_starts2, d_partners, n2, thresholds):
+        """-> (frame_offsets int64 [F+1] host, address of the device list of 2 n uint32, address of the device list of 2 n float32
+        (both context-owned until the next ring call; 0 when empty), n).  The atom indices are not checked."""
+        offs = np.zeros(F + 1, dtype=np.int64)
+        pp, pd = _vp(None), _vp(None)
+        _check(load().mkamd_ring_interactions_dev(self._h, int(kind), _ptr(d_coords), N, F, _ptr(d_box), _ptr(d_ring_atoms), n_ring_atoms,
+                                                  _ptr(d_starts1), n1, _ptr(d_starts2), _ptr(d_partners), n2, _ptr(thresholds), _ptr(offs),
+                                                  ctypes.byref(pp), ctypes.byref(pd)))
+        return offs, int(pp.value or 0), int(pd.value or 0), int(offs[-1])
 
     def dist_reduction_dev(self, d_coords, N, F, d_box, d_g1a, d_g1o, ng1, n_g1_atoms, d_g2a, d_g2o, ng2, d_ch1, d_ch2, selfdist, pairs, pbc,
                            d_masses, r1, r2, d_out):

@@ -16,6 +16,7 @@
 #include "moments_pipeline.h"
 #include "wrap_pipeline.h"
 #include "wrap_cell_pipeline.h"
+#include "ring_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "xtc_headers.h"
@@ -112,6 +113,10 @@ struct mkamd_ctx {
     void* stage_host_dev = nullptr;        // device-side address of the same memory (mapped): tiny inputs are read in place
     size_t stage_cap = 0;
     std::vector<uint32_t> contacts_host;   // result of the last mkamd_contacts_trajectory_host call (owned here)
+    std::vector<uint32_t> ring_pairs_host; // results of the last mkamd_ring_interactions_host call (owned here)
+    std::vector<float> ring_distang_host;
+    int ring_avoid = 0;                    // mkamd_ctx_set_ring_plan
+    long long ring_chunk = 0;
     std::vector<float> packed_coords;      // the selected atoms' rows of a host distance call (host_pack.h), kept between calls
     std::vector<float> f32_stage;          // host staging of big float64-out results
     struct PendingHostCall { bool active = false; size_t out_bytes = 0; bool mapped_out = false; unsigned seq = 0; void* dout = nullptr; hipEvent_t done = nullptr; };
@@ -2230,6 +2235,102 @@ try {
                                 (const uint32_t*)dch, symmetric, pbc, d2_thresholds, n_edges, (int32_t*)dout);
     if (st) return st;
     return download(ctx, counts, dout, bytes, false);
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// ring interactions (include/mkamd_distance.h "ring interactions"; ring_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_ctx_set_ring_plan(mkamd_ctx* ctx, int avoid_mask, int64_t chunk_frames)
+try {
+    if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
+    if (avoid_mask < 0 || avoid_mask > 2) return fail(MKAMD_EINVAL, "ring plan: avoid mask 0, 1 (not the frame-lane kernels) or 2 (not the pair-lane kernels)");
+    if (chunk_frames < 0) return fail(MKAMD_EINVAL, "ring plan: chunk_frames must not be negative");
+    ctx->ring_avoid = avoid_mask;
+    ctx->ring_chunk = (long long)chunk_frames;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+static mkamd::RingArgs ring_args(int kind, const float* d_coords, int64_t F, const float* d_box, const uint32_t* d_ring_atoms, int64_t n_ring_atoms,
+                                 const uint32_t* d_starts1, int64_t n1, const uint32_t* d_starts2, const uint32_t* d_partners, int64_t n2,
+                                 const uint32_t* d_emit, const float* thresholds)
+{
+    mkamd::RingArgs a;
+    a.kind = kind;
+    a.coords = d_coords; a.F = F; a.box = d_box;
+    a.ring_atoms = d_ring_atoms; a.n_ring_atoms = n_ring_atoms;
+    a.starts1 = d_starts1; a.n1 = n1; a.starts2 = d_starts2; a.partners = d_partners; a.n2 = n2;
+    a.emit = kind == mkamd::RING_PIPI ? nullptr : d_emit;
+    a.estride = kind == mkamd::RING_SIGMAHOLE ? 2 : 1;
+    for (int i = 0; i < 4; ++i) a.thr[i] = thresholds[i];
+    return a;
+}
+
+extern "C" int mkamd_ring_interactions_dev(mkamd_ctx* ctx, int kind, const float* d_coords, int64_t n_atoms, int64_t F, const float* d_box,
+                                           const uint32_t* d_ring_atoms, int64_t n_ring_atoms, const uint32_t* d_starts1, int64_t n1,
+                                           const uint32_t* d_starts2, const uint32_t* d_partners, int64_t n2, const float* thresholds,
+                                           int64_t* frame_offsets, const uint32_t** d_pairs, const float** d_distang)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (n_atoms < 0 || F < 0 || n1 < 0 || n2 < 0 || n_ring_atoms < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (!frame_offsets || !d_pairs || !d_distang || !thresholds) return fail(MKAMD_EINVAL, "frame_offsets / d_pairs / d_distang / thresholds pointer is NULL");
+    *d_pairs = nullptr;
+    *d_distang = nullptr;
+    std::string err;
+    mkamd::RingDeviceSink<mkamd_ctx> sink{*ctx};
+    static_assert(sizeof(long long) == sizeof(int64_t), "frame offsets are int64");
+    st = mkamd::run_ring_interactions(*ctx, ring_args(kind, d_coords, F, d_box, d_ring_atoms, n_ring_atoms, d_starts1, n1, d_starts2, d_partners, n2,
+                                                      d_partners, thresholds),
+                                      (size_t)256 << 20, ctx->ring_chunk, (long long*)frame_offsets, sink, err, ctx->ring_avoid);
+    if (st) return run_status(st, err);
+    if (sink.size) {
+        *d_pairs = static_cast<const uint32_t*>(sink.pairs);
+        *d_distang = static_cast<const float*>(sink.distang);
+    }
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_ring_interactions_host(mkamd_ctx* ctx, int kind, const float* coords, int64_t N, int64_t F, const float* box,
+                                            const uint32_t* ring_atoms, int64_t n_ring_atoms, const uint32_t* starts1, int64_t n1,
+                                            const uint32_t* starts2, const uint32_t* partners, int64_t n2, const float* thresholds,
+                                            int64_t* frame_offsets, const uint32_t** pairs, const float** distang)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || n1 < 0 || n2 < 0 || n_ring_atoms < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (!frame_offsets || !pairs || !distang || !thresholds) return fail(MKAMD_EINVAL, "frame_offsets / pairs / distang / thresholds pointer is NULL");
+    if (kind != mkamd::RING_PIPI && kind != mkamd::RING_CATIONPI && kind != mkamd::RING_SIGMAHOLE)
+        return fail(MKAMD_EINVAL, "kind must be 0 (pi-pi), 1 (cation-pi) or 2 (sigma-hole)");
+    ctx->ring_pairs_host.clear();
+    ctx->ring_distang_host.clear();
+    *pairs = nullptr;
+    *distang = nullptr;
+    for (int64_t f = 0; f <= F; ++f) frame_offsets[f] = 0;
+    if (F == 0 || n1 == 0 || n2 == 0) return MKAMD_OK;
+    const bool pipi = kind == mkamd::RING_PIPI;
+    if (!coords || !ring_atoms || !starts1 || (pipi ? !starts2 : !partners)) return fail(MKAMD_EINVAL, "NULL pointer");
+    const int64_t n_part = pipi ? 0 : n2 * (kind == mkamd::RING_SIGMAHOLE ? 2 : 1);
+    if ((st = check_indices(ring_atoms, n_ring_atoms, N, "ring atom")) || (st = check_indices(partners, n_part, N, "partner atom"))) return st;
+    void *dc, *db = nullptr, *da, *d1, *d2 = nullptr, *dp = nullptr, *de = nullptr;
+    HostStage up(ctx, coords, N, F, {{ring_atoms, n_ring_atoms}, {partners, n_part}});
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.list_to(WS_R_ATOMS, ring_atoms, n_ring_atoms, &da))) return st;
+    if (!pipi && (st = up.list_to(WS_R_PARTNERS, partners, n_part, &dp))) return st;
+    if ((st = up.sync())) return st;
+    if (!pipi && (st = upload(ctx, WS_R_EMIT, partners, (size_t)n_part * 4, &de))) return st;     // the list names atoms of the caller's array
+    if (box && (st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
+    if ((st = upload(ctx, WS_R_STARTS1, starts1, (size_t)(n1 + 1) * 4, &d1))) return st;
+    if (pipi && (st = upload(ctx, WS_R_STARTS2, starts2, (size_t)(n2 + 1) * 4, &d2))) return st;
+    std::string err;
+    st = mkamd::run_ring_interactions(*ctx, ring_args(kind, (const float*)dc, F, (const float*)db, (const uint32_t*)da, n_ring_atoms, (const uint32_t*)d1, n1,
+                                                      (const uint32_t*)d2, (const uint32_t*)dp, n2, (const uint32_t*)de, thresholds),
+                                      (size_t)256 << 20, ctx->ring_chunk, (long long*)frame_offsets,
+                                      mkamd::RingHostSink<mkamd_ctx>{*ctx, ctx->ring_pairs_host, ctx->ring_distang_host}, err, ctx->ring_avoid);
+    if (st) return run_status(st, err);
+    if (ctx->ring_pairs_host.empty()) return MKAMD_OK;
+    *pairs = ctx->ring_pairs_host.data();
+    *distang = ctx->ring_distang_host.data();
+    return MKAMD_OK;
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------

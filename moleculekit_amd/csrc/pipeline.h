@@ -50,6 +50,10 @@ enum WsSlot {
     WS_W_CENTRE, WS_W_STARTS, WS_W_LARGE, WS_W_SEL,
     // ... of triclinic boxes (wrap_cell_pipeline.h): the frames' records; the host entry point's box vectors and status words
     WS_W_CELL, WS_W_BOXV, WS_W_STATUS,
+    // ring interactions (ring_pipeline.h): the chunk's ring / partner records, masks, counters; the two context-owned result lists; the
+    // host entry point's lists and the second half of a chunk on its way down
+    WS_R_REC, WS_R_PART, WS_R_MASK, WS_R_CNT, WS_R_TOT, WS_R_BASE, WS_R_PAIRS, WS_R_DISTANG, WS_R_ATOMS, WS_R_STARTS1, WS_R_STARTS2, WS_R_PARTNERS,
+    WS_R_EMIT, WS_R_OUT2,
     WS_NSLOTS
 };
 
