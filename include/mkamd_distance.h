@@ -372,6 +372,41 @@ int mkamd_ring_interactions_host(mkamd_ctx* ctx, int kind, const float* coords, 
  * chunk instead of what a 256 MB workspace allows (0: default).  Every plan produces the same lists. */
 int mkamd_ctx_set_ring_plan(mkamd_ctx* ctx, int avoid_mask, int64_t chunk_frames);
 
+/* ---- hydrogen bonds of every frame (moleculekit interactions/hbonds/hbonds.pyx: `calculate`) ----
+ * The arguments are `calculate`'s:
+ *   donors uint32 [n_donors, 2]      (heavy atom, hydrogen) rows; [n_donors, 1] (heavy atoms) with ignore_hs
+ *   acceptors uint32 [n_acceptors]
+ *   sel1, sel2 uint32 [n_atoms]      per-atom flags.  intra != 0: a pair is tested where sel1[acceptor] != 0 and sel1[heavy] != 0 (sel2 is
+ *                                    not read); otherwise where (sel1[acceptor] == 1 and sel2[heavy] == 1) or (sel2[acceptor] == 1 and
+ *                                    sel1[heavy] == 1) -- always the donor's HEAVY atom.  A pair whose acceptor IS the heavy atom is skipped
+ *   dist_threshold, angle_threshold  A and degrees (the reference's defaults: 2.5, 120); squared / divided by 57.29578 as the reference does
+ * box float32 [3, n_frames]: the minimum image is applied per axis only where |d| > box / 2 and box != 0 (a zero axis is open; there is
+ * no pbc flag); box NULL: every axis open.  Every float32 operation is the reference's, rounded on its own: the
+ * wrapped vector acceptor - hydrogen and its squared length against the threshold (a NaN passes: with ignore_hs a frame of NaN
+ * coordinates reports every allowed pair, as the reference does); then heavy - hydrogen, the dot product, the ratio clamped to [-1, 1],
+ * the C library's float32 acos restated, reported where the angle is GREATER than the threshold.
+ * The work is proportional to the ALLOWED pairs (a donor row is held against the acceptors of the selection its heavy atom is not in),
+ * not to n_donors * n_acceptors.
+ * Results, the reference's order (frame; donor row; acceptor): frame_offsets int64 [n_frames + 1] (host); *triples int32 [3 n]: heavy
+ * atom, hydrogen (-1 with ignore_hs), acceptor.  The list is context-owned (NULL when n = 0) and valid until the next hydrogen-bond call
+ * on the context.
+ * _dev: coords [n_atoms, 3, n_frames] and box are device pointers and the result list is device memory; the index lists and the flags
+ * are HOST arrays in both forms -- they are sorted into classes on the host, once per call, and the kernels never read them (a table of
+ * the sorted rows goes up instead).  Every index is checked.  Not asynchronous: the counts reach the host to size the list.
+ * MKAMD_EINVAL: a NaN threshold; an atom index >= n_atoms; more than 2^30 frames, donor rows or acceptors; more than 2^31 allowed pairs. */
+int mkamd_hbonds_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t n_frames, const float* d_box, const uint32_t* donors,
+                     int64_t n_donors, const uint32_t* acceptors, int64_t n_acceptors, const uint32_t* sel1, const uint32_t* sel2,
+                     float dist_threshold, float angle_threshold, int intra, int ignore_hs, int64_t* frame_offsets, const int32_t** d_triples);
+/* host arrays; only the rows of the donors' and acceptors' atoms are packed and uploaded (csrc/host_pack.h); the list is host memory and
+ * names atoms of the caller's array. */
+int mkamd_hbonds_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const float* box, const uint32_t* donors,
+                      int64_t n_donors, const uint32_t* acceptors, int64_t n_acceptors, const uint32_t* sel1, const uint32_t* sel2,
+                      float dist_threshold, float angle_threshold, int intra, int ignore_hs, int64_t* frame_offsets, const int32_t** triples);
+/* The launch plan of the hydrogen-bond calls (tests, same-box A-B timing).  avoid_mask: 1 not the kernels whose lanes run along frames,
+ * 2 not those whose lanes run along the acceptors of one frame (default 0: by the shape of the call).  chunk_frames > 0: that many frames
+ * per chunk instead of what a 256 MB workspace allows (0: default, a multiple of 64).  Every plan produces the same list. */
+int mkamd_ctx_set_hbond_plan(mkamd_ctx* ctx, int avoid_mask, int64_t chunk_frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,12 @@ SIGNATURES = {
     "mkamd_ring_interactions_host": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp,
                                               ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "mkamd_ctx_set_ring_plan": (_c_int, [_vp, _c_int, _c_i64]),
+    # include/mkamd_distance.h, hydrogen bonds
+    "mkamd_hbonds_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _c_int, _c_int,
+                                  _vp, ctypes.POINTER(_vp)]),
+    "mkamd_hbonds_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _c_int, _c_int,
+                                   _vp, ctypes.POINTER(_vp)]),
+    "mkamd_ctx_set_hbond_plan": (_c_int, [_vp, _c_int, _c_i64]),
 }
 
 _lib = None
@@ -394,6 +400,11 @@ class Context:
         kernels; ``chunk_frames`` > 0 forces the frames per chunk.  Every plan produces the same lists (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_ring_plan(self._h, int(avoid_mask), int(chunk_frames)))
 
+    def set_hbond_plan(self, avoid_mask: int = 0, chunk_frames: int = 0):
+        """The launch plan of the hydrogen-bond calls (include/mkamd_distance.h): avoid 1 the frame-lane kernels, 2 the pair-lane
+        kernels; ``chunk_frames`` > 0 forces the frames per chunk.  Every plan produces the same list (tests, A-B timing)."""
+        _check(load().mkamd_ctx_set_hbond_plan(self._h, int(avoid_mask), int(chunk_frames)))
+
     def set_reduction_block(self, block: int = 0):
         """0: choose; 4 / 8: first-group atoms a wave of the closest-atom group reduction keeps in registers; -1: the generic kernel."""
         _check(load().mkamd_ctx_set_reduction_block(self._h, int(block)))
@@ -555,6 +566,29 @@ class Context:
                                                   _ptr(d_starts1), n1, _ptr(d_starts2), _ptr(d_partners), n2, _ptr(thresholds), _ptr(offs),
                                                   ctypes.byref(pp), ctypes.byref(pd)))
         return offs, int(pp.value or 0), int(pd.value or 0), int(offs[-1])
+
+    def hbonds_host(self, coords, box, donors, acceptors, sel1, sel2, dist_threshold, angle_threshold, intra, ignore_hs):
+        """-> (frame_offsets int64 [F+1], triples int32 [n, 3]) -- decided and compacted on the GPU."""
+        N, _, F = coords.shape
+        offs = np.zeros(F + 1, dtype=np.int64)
+        pt = _vp(None)
+        _check(load().mkamd_hbonds_host(self._h, _ptr(coords), N, F, _ptr(box), _ptr(donors), donors.shape[0], _ptr(acceptors), acceptors.shape[0],
+                                        _ptr(sel1), _ptr(sel2), float(dist_threshold), float(angle_threshold), int(bool(intra)), int(bool(ignore_hs)),
+                                        _ptr(offs), ctypes.byref(pt)))
+        n = int(offs[-1])
+        if n == 0 or not pt.value:
+            return offs, np.zeros((0, 3), dtype=np.int32)
+        return offs, np.frombuffer((ctypes.c_int32 * (3 * n)).from_address(pt.value), dtype=np.int32).reshape(n, 3).copy()   # context-owned: copied
+
+    def hbonds_dev(self, d_coords, N, F, d_box, donors, nd, acceptors, na, sel1, sel2, dist_threshold, angle_threshold, intra, ignore_hs):
+        """coords and box on the device, the lists and flags numpy arrays -> (frame_offsets int64 [F+1] host, address of the device list
+        of 3 n int32 (context-owned until the next hydrogen-bond call; 0 when empty), n)."""
+        offs = np.zeros(F + 1, dtype=np.int64)
+        pt = _vp(None)
+        _check(load().mkamd_hbonds_dev(self._h, _ptr(d_coords), N, F, _ptr(d_box), _ptr(donors), nd, _ptr(acceptors), na, _ptr(sel1), _ptr(sel2),
+                                       float(dist_threshold), float(angle_threshold), int(bool(intra)), int(bool(ignore_hs)), _ptr(offs),
+                                       ctypes.byref(pt)))
+        return offs, int(pt.value or 0), int(offs[-1])
 
     def dist_reduction_dev(self, d_coords, N, F, d_box, d_g1a, d_g1o, ng1, n_g1_atoms, d_g2a, d_g2o, ng2, d_ch1, d_ch2, selfdist, pairs, pbc,
                            d_masses, r1, r2, d_out):

@@ -17,6 +17,7 @@
 #include "wrap_pipeline.h"
 #include "wrap_cell_pipeline.h"
 #include "ring_pipeline.h"
+#include "hbond_pipeline.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "xtc_headers.h"
@@ -117,6 +118,9 @@ struct mkamd_ctx {
     std::vector<float> ring_distang_host;
     int ring_avoid = 0;                    // mkamd_ctx_set_ring_plan
     long long ring_chunk = 0;
+    std::vector<int> hbond_triples_host;   // result of the last mkamd_hbonds_host call (owned here)
+    int hbond_avoid = 0;                   // mkamd_ctx_set_hbond_plan
+    long long hbond_chunk = 0;
     std::vector<float> packed_coords;      // the selected atoms' rows of a host distance call (host_pack.h), kept between calls
     std::vector<float> f32_stage;          // host staging of big float64-out results
     struct PendingHostCall { bool active = false; size_t out_bytes = 0; bool mapped_out = false; unsigned seq = 0; void* dout = nullptr; hipEvent_t done = nullptr; };
@@ -2330,6 +2334,83 @@ try {
     if (ctx->ring_pairs_host.empty()) return MKAMD_OK;
     *pairs = ctx->ring_pairs_host.data();
     *distang = ctx->ring_distang_host.data();
+    return MKAMD_OK;
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// hydrogen bonds (include/mkamd_distance.h "hydrogen bonds"; hbond_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_ctx_set_hbond_plan(mkamd_ctx* ctx, int avoid_mask, int64_t chunk_frames)
+try {
+    if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
+    if (avoid_mask < 0 || avoid_mask > 2) return fail(MKAMD_EINVAL, "hbond plan: avoid mask 0, 1 (not the frame-lane kernels) or 2 (not the pair-lane kernels)");
+    if (chunk_frames < 0) return fail(MKAMD_EINVAL, "hbond plan: chunk_frames must not be negative");
+    ctx->hbond_avoid = avoid_mask;
+    ctx->hbond_chunk = (long long)chunk_frames;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_hbonds_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t F, const float* d_box, const uint32_t* donors,
+                                int64_t n_donors, const uint32_t* acceptors, int64_t n_acceptors, const uint32_t* sel1, const uint32_t* sel2,
+                                float dist_threshold, float angle_threshold, int intra, int ignore_hs, int64_t* frame_offsets, const int32_t** d_triples)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (n_atoms < 0 || F < 0 || n_donors < 0 || n_acceptors < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (!frame_offsets || !d_triples) return fail(MKAMD_EINVAL, "frame_offsets / d_triples pointer is NULL");
+    *d_triples = nullptr;
+    mkamd::HbondArgs a;
+    a.coords = d_coords; a.n_atoms = n_atoms; a.F = F; a.box = d_box;
+    a.donors = donors; a.nd = n_donors; a.acceptors = acceptors; a.na = n_acceptors; a.sel1 = sel1; a.sel2 = sel2;
+    a.dist_threshold = dist_threshold; a.angle_threshold = angle_threshold; a.intra = intra != 0; a.ignore_hs = ignore_hs != 0;
+    std::string err;
+    mkamd::HbondDeviceSink<mkamd_ctx> sink{*ctx};
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "frame offsets are int64, triples int32");
+    st = mkamd::run_hbonds(*ctx, a, (size_t)256 << 20, ctx->hbond_chunk, (long long*)frame_offsets, sink, err, ctx->hbond_avoid);
+    if (st) return run_status(st, err);
+    if (sink.size) *d_triples = static_cast<const int32_t*>(sink.triples);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_hbonds_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const float* box, const uint32_t* donors, int64_t n_donors,
+                                 const uint32_t* acceptors, int64_t n_acceptors, const uint32_t* sel1, const uint32_t* sel2, float dist_threshold,
+                                 float angle_threshold, int intra, int ignore_hs, int64_t* frame_offsets, const int32_t** triples)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || n_donors < 0 || n_acceptors < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (!frame_offsets || !triples) return fail(MKAMD_EINVAL, "frame_offsets / triples pointer is NULL");
+    ctx->hbond_triples_host.clear();
+    *triples = nullptr;
+    for (int64_t f = 0; f <= F; ++f) frame_offsets[f] = 0;
+    if (dist_threshold != dist_threshold || angle_threshold != angle_threshold) return fail(MKAMD_EINVAL, "a threshold is NaN");
+    if (F > 0x3fffffffLL || n_donors > 0x3fffffffLL || n_acceptors > 0x3fffffffLL) return fail(MKAMD_EINVAL, "too many frames, donor rows or acceptors (> 2^30)");
+    if (F == 0 || n_donors == 0 || n_acceptors == 0) return MKAMD_OK;
+    if (!coords || !donors || !acceptors || !sel1 || (!intra && !sel2)) return fail(MKAMD_EINVAL, "NULL pointer");
+    const int64_t n_don = n_donors * (ignore_hs ? 1 : 2);
+    if ((st = check_indices(donors, n_don, N, "donor atom")) || (st = check_indices(acceptors, n_acceptors, N, "acceptor atom"))) return st;
+    void *dc, *db = nullptr;
+    HostStage up(ctx, coords, N, F, {{donors, n_don}, {acceptors, n_acceptors}});
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.sync())) return st;
+    if (box && (st = upload(ctx, WS_H_BOX, box, (size_t)3 * F * 4, &db))) return st;
+    // the lists in the numbering of the rows that went up; the list names the caller's atoms
+    std::vector<uint32_t> pd, pa, p1, p2;
+    mkamd::HbondArgs a;
+    a.coords = (const float*)dc; a.n_atoms = up.rows(); a.F = F; a.box = (const float*)db;
+    a.donors = donors; a.nd = n_donors; a.acceptors = acceptors; a.na = n_acceptors; a.sel1 = sel1; a.sel2 = sel2;
+    if (up.pk.on) {
+        pd = up.pk.remap(donors, n_don); pa = up.pk.remap(acceptors, n_acceptors); p1 = up.pk.gather(sel1);
+        if (!intra) p2 = up.pk.gather(sel2);
+        a.donors = pd.data(); a.acceptors = pa.data(); a.sel1 = p1.data(); a.sel2 = intra ? nullptr : p2.data();
+        a.names = up.pk.uniq.data();
+    }
+    a.dist_threshold = dist_threshold; a.angle_threshold = angle_threshold; a.intra = intra != 0; a.ignore_hs = ignore_hs != 0;
+    std::string err;
+    st = mkamd::run_hbonds(*ctx, a, (size_t)256 << 20, ctx->hbond_chunk, (long long*)frame_offsets,
+                           mkamd::HbondHostSink<mkamd_ctx>{*ctx, ctx->hbond_triples_host}, err, ctx->hbond_avoid);
+    if (st) return run_status(st, err);
+    if (!ctx->hbond_triples_host.empty()) *triples = ctx->hbond_triples_host.data();
     return MKAMD_OK;
 } MK_API_CATCH
 

@@ -54,6 +54,8 @@ enum WsSlot {
     // host entry point's lists and the second half of a chunk on its way down
     WS_R_REC, WS_R_PART, WS_R_MASK, WS_R_CNT, WS_R_TOT, WS_R_BASE, WS_R_PAIRS, WS_R_DISTANG, WS_R_ATOMS, WS_R_STARTS1, WS_R_STARTS2, WS_R_PARTNERS,
     WS_R_EMIT, WS_R_OUT2,
+    // hydrogen bonds (hbond_pipeline.h): the call's table (rows, sublists, tile numbering); the chunk's masks and counters; the context-owned list
+    WS_HB_TABLE, WS_HB_MASK, WS_HB_CNT, WS_HB_TOT, WS_HB_BASE, WS_HB_TRIPLES,
     WS_NSLOTS
 };
 
