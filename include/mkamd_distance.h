@@ -98,6 +98,21 @@ int mkamd_pdist_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n, int32_t di
  * of the first one.  Run by the GPU test tier. */
 int mkamd_selftest_sqrt(mkamd_ctx* ctx, uint64_t* mismatches, uint32_t* first_bad_bits);
 
+/* Self-test of the device arithmetic under the bit-exact kernels (csrc/arith_probe.h): operation `op` applied elementwise to n
+ * elements of the device arrays a, b, c (those the operation reads; the others may be NULL) into the device array `out`, by a
+ * kernel that calls the very function the product's kernels call.  The element width is fixed by the operation:
+ *    0 fadd, 1 fsub, 2 fmul (a, b), 3 fmul_add (a * b + c, two roundings), 5 fdiv, 6 ring_div, 13 round(a / b) of the distance
+ *    kernels, 19 the rings' round(a / b), 14 the squared minimum-image separation of a in a box b, 16 the dihedrals' wrap of a
+ *    in a box b, 8 fsqrt, 9 ring_sqrt, 10 roundf, 11 rint, 17 the restated acosf: float32 in, float32 out;
+ *    20 the same separation and its negative through the packed form (dist2_pk): float32 in, THREE float32 out per element (the two
+ *    squared separations; 1 where the accumulated test tells the caller to redo the pair with the form of 14, else 0);
+ *    15 the wrap's decision (group centre a, box centre b, box c): float32 in, TWO float32 out per element (1 or 0: moved; the translation);
+ *    12 round((double)a), 18 the folded angle in degrees of a: float32 in, float64 out;
+ *    4 dmul_add (a * b + c, two roundings), 7 ddiv: float64 in, float64 out.
+ * Consecutive elements are consecutive lanes (64 to a wave, 256 to a block).  Launched on the context's stream; the call does not
+ * wait.  Run by the GPU test tier against independent references, bit for bit. */
+int mkamd_selftest_arith(mkamd_ctx* ctx, int op, long long n, const void* a, const void* b, const void* c, void* out);
+
 /* Which kernels dist_trajectory may take (default 0: all; the choice depends on the shape of the call): bits of `avoid_mask` --
  * 1 the block-per-frame kernel (rectangular calls with short rows -- the small calls MetricDistance makes: one launch), 2 the row
  * kernel (rectangular calls with rows of >= 64 second atoms), 4 the rectangular tile kernel, 8 the row kernel's 16-byte stores,

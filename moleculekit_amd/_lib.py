@@ -111,6 +111,7 @@ SIGNATURES = {
     "mkamd_pdist_dev": (_c_int, [_vp, _vp, _c_i64, _c_i32, _vp]),
     "mkamd_ctx_set_reduction_block": (_c_int, [_vp, _c_int]),
     "mkamd_selftest_sqrt": (_c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
+    "mkamd_selftest_arith": (_c_int, [_vp, _c_int, ctypes.c_longlong, _vp, _vp, _vp, _vp]),
     "mkamd_ctx_set_dist_kernels": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_last_dist_kernel": (_c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t]),
     "mkamd_cdist_host": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _vp]),
@@ -155,6 +156,19 @@ SIGNATURES = {
     "mkamd_hbonds_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _c_int, _c_int,
                                    _vp, ctypes.POINTER(_vp)]),
     "mkamd_ctx_set_hbond_plan": (_c_int, [_vp, _c_int, _c_i64]),
+}
+
+# operations of mkamd_selftest_arith (csrc/arith_probe.h): name -> (code, arrays read, their dtype, result dtype, results per element)
+ARITH_OPS = {
+    "fadd": (0, 2, np.float32, np.float32, 1), "fsub": (1, 2, np.float32, np.float32, 1), "fmul": (2, 2, np.float32, np.float32, 1),
+    "fmul_add": (3, 3, np.float32, np.float32, 1), "dmul_add": (4, 3, np.float64, np.float64, 1),
+    "fdiv": (5, 2, np.float32, np.float32, 1), "ring_div": (6, 2, np.float32, np.float32, 1), "ddiv": (7, 2, np.float64, np.float64, 1),
+    "fsqrt": (8, 1, np.float32, np.float32, 1), "ring_sqrt": (9, 1, np.float32, np.float32, 1),
+    "roundf": (10, 1, np.float32, np.float32, 1), "rint": (11, 1, np.float32, np.float32, 1), "dround": (12, 1, np.float32, np.float64, 1),
+    "round_quot": (13, 2, np.float32, np.float32, 1), "min_image": (14, 2, np.float32, np.float32, 1),
+    "wrap_decide": (15, 3, np.float32, np.float32, 2), "dih_wrap": (16, 2, np.float32, np.float32, 1),
+    "acosf": (17, 1, np.float32, np.float32, 1), "ring_angle": (18, 1, np.float32, np.float64, 1),
+    "ring_round_quot": (19, 2, np.float32, np.float32, 1), "min_image_pk": (20, 2, np.float32, np.float32, 3),
 }
 
 _lib = None
@@ -388,6 +402,26 @@ class Context:
         n, first = ctypes.c_uint64(0), ctypes.c_uint32(0)
         _check(load().mkamd_selftest_sqrt(self._h, ctypes.byref(n), ctypes.byref(first)))
         return int(n.value), int(first.value)
+
+    def arith_probe(self, op, a, b=None, c=None):
+        """One operation of the device arithmetic under the bit-exact kernels (``ARITH_OPS``: a name or its code), elementwise over
+        numpy arrays of equal length (include/mkamd_distance.h, mkamd_selftest_arith): the arrays go to the device as they are, bit
+        for bit, and the result comes back the same way -- [n], or [n, k] for the operations with k results per element.  The result array is filled with a
+        sentinel (every byte 0xA5) before the kernel runs."""
+        import torch
+        code, arity, in_dt, out_dt, cols = ARITH_OPS[op] if isinstance(op, str) else next(v for v in ARITH_OPS.values() if v[0] == int(op))
+        ins = [np.ascontiguousarray(x, in_dt).ravel() for x in (a, b, c)[:arity]]
+        if any(x is not None for x in (a, b, c)[arity:]) or any(x.size != ins[0].size for x in ins):
+            raise ValueError(f"arith_probe: operation {op} takes {arity} arrays of equal length")
+        n = ins[0].size
+        dev = torch.device("cuda", self.device)
+        d_in = [torch.from_numpy(x).to(dev) for x in ins] + [None] * (3 - arity)
+        d_out = torch.full((n * cols * np.dtype(out_dt).itemsize,), 0xA5, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)                 # the arrays are in place before the context's stream (whichever it is) reads them
+        _check(load().mkamd_selftest_arith(self._h, code, n, _ptr(d_in[0]), _ptr(d_in[1]), _ptr(d_in[2]), _ptr(d_out)))
+        self.synchronize()
+        out = d_out.cpu().numpy().view(out_dt)
+        return out.reshape(n, cols) if cols > 1 else out
 
     def set_dist_kernels(self, avoid_mask: int = 0):
         """Kernels dist_trajectory must NOT take (include/mkamd_distance.h): 1 block-per-frame, 2 rows, 4 rectangular tiles, 8 the

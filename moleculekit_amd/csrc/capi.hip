@@ -18,6 +18,7 @@
 #include "wrap_cell_pipeline.h"
 #include "ring_pipeline.h"
 #include "hbond_pipeline.h"
+#include "arith_probe.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "xtc_headers.h"
@@ -676,6 +677,17 @@ try {
     *mismatches = (uint64_t)host[0];
     if (first_bad_bits) *first_bad_bits = (uint32_t)(host[1] & 0xffffffffull);
     return MKAMD_OK;
+} MK_API_CATCH
+
+// one device function per `op` (arith_probe.h), elementwise over device arrays, on the context's stream: asynchronous
+int mkamd_selftest_arith(mkamd_ctx* ctx, int op, long long n, const void* a, const void* b, const void* c, void* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    const char* err = nullptr;
+    st = run_arith_probe(*ctx, op, n, a, b, c, out, err);
+    if (err) return fail(MKAMD_EINVAL, err);
+    return st;
 } MK_API_CATCH
 
 // Every distance kernel takes its roots with mk_fsqrt_rn_ordinary, whose correct rounding is a PROPERTY OF THIS CHIP's v_rsq_f32 (checked

@@ -24,10 +24,12 @@ namespace mkamd {
 // that close to a half-integer (where round() changes its value) both round to the same integer -- and away from the
 // half-integers round-half-away (C round) and round-half-even (ONE instruction, v_rndne_f32) agree as well.  With
 // r = rndne(q) the distance of q from the nearest half-integer is 0.5 - |q - r| (the subtraction is exact).  The three
-// axes share ONE test: the largest |q - r| against the bound of the largest |q| (two v_max3_f32, an fma, a compare).
+// axes share ONE test: the largest |q - r| against the bound of the three |q| (a v_max3_f32, two adds, an fma, a compare).
 // Pairs that fail it -- and everything that is not an ordinary number: a zero box makes q infinite, the bound -inf and
-// the comparison false -- take the correctly rounded divisions.  (A NaN q is ignored by the maxima; then r is NaN and so
-// is the reference's result: 0 / 0, inf / inf or a NaN operand.)
+// the comparison false -- take the correctly rounded divisions.  The bound is taken from |qx| + |qy| + |qz|, not from the largest
+// of them: at least as strict, and a NaN q makes it a NaN, which fails the comparison too.  (The maxima ignore a NaN, and a NaN
+// q is not always a NaN in the reference: a box edge below 2^-128 has an INFINITE reciprocal, and a zero separation times it is
+// a NaN where d / b is 0 and the reference's result d -- found by the arithmetic probe, arith_probe.h.)
 // `ib` = fl(1 / b), computed once per (lane, frame) instead of three IEEE divisions per pair.
 // (Round 5 tried the test on the SHIFTED separation instead -- |d - b r| < b (1/2 - 2^-12) per axis and |q| < 512: three compares
 //  against per-frame constants, a max3 and a compare where this takes seven instructions; same results, emulator and GPU tests
@@ -38,6 +40,19 @@ namespace mkamd {
 //  this form on every periodic shape of tools/dist_shapes_probe.py, three alternating runs each: not adopted.)
 MK_DEV float round_quotient_exact(float d, float b) { return roundf(mk_fdiv_rn(d, b)); }
 
+// |a| + |b| + |c| (two v_add_f32 with |x| source modifiers): an upper bound of the largest of the three that, unlike mk_max3 and its
+// kin, does NOT ignore a NaN operand -- what guards a shortcut must see it.  (Built from the primitives every provider of the device
+// API has: nothing new for a host emulation to supply.)
+MK_DEV float drc_sum3_abs(float a, float b, float c) { return mk_fadd_rn(mk_fadd_rn(mk_abs(a), mk_abs(b)), mk_abs(c)); }
+// The largest BIT PATTERN of three floats none of which is a negative number (v_max3_u32): for numbers that is the largest value, and
+// a NaN -- its pattern lies above every number's -- wins instead of being ignored.
+MK_DEV float drc_max3_bits(float m, float a, float b)
+{
+    const unsigned um = mk_float_bits(m), ua = mk_float_bits(a), ub = mk_float_bits(b);
+    const unsigned t = ua > ub ? ua : ub;
+    return mk_uint_as_float(t > um ? t : um);
+}
+
 // distance_utils.pyx:34-54 (_dist) / :188-206 (_dist2)
 MK_DEV float dist2_min_image_f32(float x1, float y1, float z1, float x2, float y2, float z2,
                                  float bx, float by, float bz, float ibx, float iby, float ibz, bool wrap)
@@ -47,7 +62,7 @@ MK_DEV float dist2_min_image_f32(float x1, float y1, float z1, float x2, float y
         const float qx = mk_fmul_rn(dx, ibx), qy = mk_fmul_rn(dy, iby), qz = mk_fmul_rn(dz, ibz);
         float rx = mk_rint(qx), ry = mk_rint(qy), rz = mk_rint(qz);
         const float tm = mk_max3(fabsf(qx - rx), fabsf(qy - ry), fabsf(qz - rz));
-        const float qm = mk_max3(fabsf(qx), fabsf(qy), fabsf(qz));
+        const float qm = drc_sum3_abs(qx, qy, qz);                  // >= the largest |q|, and a NaN if any q is one
         if (!(tm < mk_fma(-3e-7f, qm, 0.5f))) {
             asm volatile("" ::: "memory");                           // a real branch: the divisions must not be computed "just in case"
             rx = round_quotient_exact(dx, bx); ry = round_quotient_exact(dy, by); rz = round_quotient_exact(dz, bz);
@@ -71,7 +86,8 @@ MK_DEV mk_f2 dist2_x2(float x1, float y1, float z1, mk_f2 x2, mk_f2 y2, mk_f2 z2
 }
 
 // The image integers of SEVERAL pairs behind one wave-uniform test (round 6; the group reductions first, then the pair-table walk):
-// risk = max over the pairs of (largest |q - rndne(q)| + 3e-7 largest |q|), accumulated without a branch; a stretch whose risk
+// risk = max over the pairs of (largest |q - rndne(q)| + 3e-7 (|qx| + |qy| + |qz|)), accumulated without a branch -- as bit patterns, so
+// that a NaN (a q that is one) is kept, not ignored; a stretch whose risk
 // reaches DRC_RISK in any lane is computed once more pair by pair (dist2_min_image_f32: the per-pair test, the divisions).
 constexpr float DRC_RISK = 0.4999998f;               // risk below this: every rndne(d * fl(1/b)) is the reference's round(d / b)
                                                      // (the per-pair test is tm < 0.5 - 3e-7 qm, proven bound 1.8e-7 qm; here
@@ -87,9 +103,9 @@ MK_DEV mk_f2 dist2_pk(mk_f2 ax, mk_f2 ay, mk_f2 az, float x2, float y2, float z2
         const mk_f2 qx = mk_f2_mul_rn(dx, mk_f2_splat(ibx)), qy = mk_f2_mul_rn(dy, mk_f2_splat(iby)), qz = mk_f2_mul_rn(dz, mk_f2_splat(ibz));
         const mk_f2 rx = mk_f2{mk_rint(qx[0]), mk_rint(qx[1])}, ry = mk_f2{mk_rint(qy[0]), mk_rint(qy[1])}, rz = mk_f2{mk_rint(qz[0]), mk_rint(qz[1])};
         const mk_f2 tx = mk_f2_sub_rn(qx, rx), ty = mk_f2_sub_rn(qy, ry), tz = mk_f2_sub_rn(qz, rz);       // (exact)
-        const float s0 = mk_fma(3e-7f, mk_max3_abs_raw(qx[0], qy[0], qz[0]), mk_max3_abs_raw(tx[0], ty[0], tz[0]));
-        const float s1 = mk_fma(3e-7f, mk_max3_abs_raw(qx[1], qy[1], qz[1]), mk_max3_abs_raw(tx[1], ty[1], tz[1]));
-        risk = mk_max3_raw(risk, s0, s1);
+        const float s0 = mk_fma(3e-7f, drc_sum3_abs(qx[0], qy[0], qz[0]), mk_max3_abs_raw(tx[0], ty[0], tz[0]));
+        const float s1 = mk_fma(3e-7f, drc_sum3_abs(qx[1], qy[1], qz[1]), mk_max3_abs_raw(tx[1], ty[1], tz[1]));
+        risk = drc_max3_bits(risk, s0, s1);                       // (none of them negative: a NaN stays, and fails the caller's test)
         dx = mk_f2_sub_rn(dx, mk_f2_mul_rn(mk_f2_splat(bx), rx));
         dy = mk_f2_sub_rn(dy, mk_f2_mul_rn(mk_f2_splat(by), ry));
         dz = mk_f2_sub_rn(dz, mk_f2_mul_rn(mk_f2_splat(bz), rz));
@@ -1489,7 +1505,8 @@ MK_KERNEL(DRF_THREADS) void k_dist_reduction_few(const float* __restrict__ c1, c
 //    pairs, plus three v_rndne_f32 per pair.  Nothing is selected per pair: whether a group pair wraps (pbc and different
 //    chains, :225-229) is wave-uniform.
 //  * The exactness test of the image integers (round_quotient_exact above) is ACCUMULATED: risk = max over the pairs of
-//    (largest |q - rndne(q)| + 3e-7 largest |q|) -- two v_max3 with |x| modifiers, an fma and half a v_max3 per pair, no branch.
+//    (largest |q - rndne(q)| + 3e-7 (|qx| + |qy| + |qz|)) -- a v_max3 and two adds with |x| modifiers, an fma and half a v_max3_u32 per
+//    pair, no branch (dist2_pk: a NaN q must fail the test, so it is summed, not ignored by a maximum).
 //    One wave-uniform test per (block of first atoms, second group); a stretch that fails it (a separation within 3e-7 of half
 //    a box length, an infinite quotient) is redone pair by pair with dist2_min_image_f32 and its correctly rounded divisions.
 //  * The reference's update `if dist2 < mindist or mindist < 0` (mindist = -1 at first) keeps the FIRST pair's d^2 whatever it

@@ -299,6 +299,87 @@ def test_block_per_frame_kernel_over_many_blocks_and_every_kernel_on_the_same_sh
     assert {"mkamd::k_dist_frame", "mkamd::k_dist_rect", "mkamd::k_build_atom_pairs + mkamd::k_dist_pairs", "mkamd::k_sel_to_frames + mkamd::k_dist_rows"} <= seen, seen
 
 
+def _scaled_trajectory(rng, N, F, exponents, coincident_frames):
+    """coordinates and boxes of frame f scaled by 10^exponents[f % len]; atoms 0 and 1 (of different chains) coincide in the given frames"""
+    scale = np.array([10.0 ** exponents[f % len(exponents)] for f in range(F)])
+    c = (rng.uniform(-40, 40, size=(N, 3, F)) * scale[None, None, :]).astype(np.float32)
+    b = (rng.uniform(30, 45, size=(3, F)) * scale[None, :]).astype(np.float32)
+    for f in coincident_frames:
+        c[1, :, f] = c[0, :, f]
+    ch = rng.integers(0, 5, size=N).astype(np.uint32)
+    ch[0], ch[1] = 0, 1
+    return c, b, ch
+
+
+def _selections_with_atoms_0_and_1(rng, N, selfd, n1, n2):
+    s2 = (2 + rng.choice(N - 2, n2, replace=False)).astype(np.uint32)
+    s2[0] = 1
+    if selfd:
+        s2[1] = 0
+        return s2[:n1].copy(), s2
+    s1 = (2 + rng.choice(N - 2, n1, replace=False)).astype(np.uint32)
+    s1[0] = 0
+    return s1, s2
+
+
+def _every_kernel_against_the_oracle(ctx, c, b, ch, rng, shapes, avoids):
+    N, _, F = c.shape
+    seen = set()
+    try:
+        for selfd, n1, n2 in shapes:
+            s1, s2 = _selections_with_atoms_0_and_1(rng, N, selfd, n1, n2)
+            for pbc in (False, True):
+                for squared in (False, True):
+                    exp = oracle.dist_trajectory(c, b, s1, s2, ch, selfd, pbc, squared=squared)
+                    for avoid in avoids:
+                        ctx.set_dist_kernels(avoid)
+                        r = np.full(exp.shape, -3.0, np.float32)
+                        ctx.dist_trajectory_host(c, b, s1, s2, ch, selfd, pbc, squared, r)
+                        seen.add(ctx.last_dist_kernel().split("<")[0])
+                        same = (r.view(np.uint32) == exp.view(np.uint32)) | (np.isnan(r) & np.isnan(exp))
+                        assert same.all(), (selfd, n1, n2, pbc, squared, avoid, ctx.last_dist_kernel(), int((~same).sum()),
+                                            np.argwhere(~same)[0].tolist(), r[~same][0], exp[~same][0])
+                        assert np.array_equal(r, exp, equal_nan=True)
+    finally:
+        ctx.set_dist_kernels(0)
+    return seen
+
+
+def test_every_kernel_at_the_extremes_of_float32():
+    """The arithmetic probe's extremes (tests/test_gpu_arith.py) through the real kernels: the shapes that between them take every
+    dist_trajectory kernel (20 x 256 is there for the row kernel, which none of the others reaches at 70 frames), with the coordinates AND the box of frame f scaled by 10^s, s cycling through -24, -20, 0, 18, 20 -- squared
+    distances that are denormal, below 2^-96 (the root's scaled branch), ordinary, huge, and infinite (inf - inf in the image shift, a
+    root of inf) -- and one frame in which two atoms of different chains coincide (a zero separation; a root of zero).  Periodic and
+    open, squared and not, under avoid masks 0, 1, 2, 3 and 16: bit for bit the oracle's, a NaN for a NaN, a sentinel in every
+    element first."""
+    from moleculekit_amd import _lib
+    ctx = _lib.default_context()
+    rng = np.random.default_rng(47)
+    c, b, ch = _scaled_trajectory(rng, 400, 70, (-24, -20, 0, 18, 20), coincident_frames=(7,))
+    with np.errstate(all="ignore"):
+        d2 = oracle.dist_trajectory(c, b, np.arange(40, dtype=np.uint32), np.arange(40, 80, dtype=np.uint32), ch, False, False, squared=True)
+    kinds = [((d2[f] > 0) & (d2[f] < 2.0 ** -126)).any() for f in range(5)], [np.isinf(d2[f]).any() for f in range(5)]
+    assert kinds[0][0] and ((d2[1] > 2.0 ** -126) & (d2[1] < 2.0 ** -96)).any() and kinds[1][4] and np.isfinite(d2[3]).any()
+    seen = _every_kernel_against_the_oracle(ctx, c, b, ch, rng, [(False, 300, 30), (False, 41, 101), (True, 61, 61), (False, 5, 300), (False, 20, 256)],
+                                            (0, 1, 2, 3, 16))
+    assert {"mkamd::k_dist_frame", "mkamd::k_dist_rect", "mkamd::k_build_atom_pairs + mkamd::k_dist_pairs", "mkamd::k_sel_to_frames + mkamd::k_dist_rows"} <= seen, seen
+
+
+def test_a_box_whose_reciprocal_overflows_and_a_zero_separation():
+    """Found by the arithmetic probe: a box edge below 2^-128 has an infinite float32 reciprocal, and the image shortcut's quotient of
+    a ZERO separation is then 0 x inf, a NaN -- which the maxima of its exactness test ignored, so the pair came out NaN where the
+    reference's 0 / b is 0 and the distance 0.  Every frame here is scaled by 10^-41 (boxes of 3e-40 .. 4.5e-40) and has two coincident
+    atoms of different chains; every kernel, periodic and open: the oracle's bits."""
+    from moleculekit_amd import _lib
+    ctx = _lib.default_context()
+    rng = np.random.default_rng(53)
+    c, b, ch = _scaled_trajectory(rng, 400, 9, (-41,), coincident_frames=range(9))
+    assert (b > 0).all() and (b < 2.0 ** -128).all()
+    exp = oracle.dist_trajectory(c, b, np.array([0], np.uint32), np.array([1], np.uint32), ch, False, True)
+    assert (exp == 0).all()
+    _every_kernel_against_the_oracle(ctx, c, b, ch, rng, [(False, 300, 30), (True, 61, 61), (False, 5, 300), (False, 20, 256)], (0, 1, 2, 3, 16))
+
+
 def test_results_at_four_byte_alignment_take_the_sixteen_byte_stores():
     """Round 5: every kernel stores 16 bytes per lane at whatever alignment a result row has (rows of an odd pitch -- the triangular
     list of 450 atoms has 101 025 pairs --, a result pointer that is an offset view: 4-byte aligned only).  The same calls into an
