@@ -1521,11 +1521,29 @@ constexpr int SURV_OFF_BITS = 10;
 // box (columns out of reach altogether are dropped).  The candidates are numbered 0..N-1 across the runs (`pre` = a
 // run's first number) and visited in chunks of 64 consecutive numbers, so that a chunk is full whatever the runs'
 // lengths are.  Found once per tile and shared by every traversal.
+// The number -> record mapping is monotone and the chunks of a traversal are issued in rising order, so a traversal keeps
+// a CURSOR (CandCursor) instead of searching the runs again in every chunk.  The cursor is wave-uniform -- the run that
+// holds the chunk's first number -- because a chunk lies inside one run more often than not; the runs that hold records
+// are a mask (`held`: the empty ones are never visited), and a run's first number is the end of the run visited before it.
 struct CandRuns {
     unsigned r0, len, pre, N, T;
+    unsigned end;                     // pre + len
+    unsigned long long held;          // wave-uniform: the runs that hold records
     bool codable;                     // every run is short enough for the 16-bit survivor codes
     MK_PHASE_FIELDS
 };
+
+// the scan over the runs' lengths (cr.r0 and cr.len are set)
+MK_DEV void link_candidate_runs(CandRuns& cr)
+{
+    const unsigned incl = wave_scan_inclusive(cr.len);
+    cr.pre = incl - cr.len;
+    cr.end = incl;
+    cr.N = mk_readlane(incl, WAVE - 1);
+    cr.T = (cr.N + (WAVE - 1)) >> 6;
+    cr.codable = mk_ballot(cr.len > (1u << SURV_OFF_BITS)) == 0ull;      // (run index < 64: 6 bits)
+    cr.held = mk_ballot(cr.len != 0u);
+}
 
 template <int K>
 MK_DEV CandRuns find_candidate_runs(const GridDesc& g, const TileGeom& tg, const unsigned* __restrict__ cell_start)
@@ -1592,11 +1610,7 @@ MK_DEV CandRuns find_candidate_runs(const GridDesc& g, const TileGeom& tg, const
         }
     }
     }
-    const unsigned incl = wave_scan_inclusive(cr.len);
-    cr.pre = incl - cr.len;
-    cr.N = mk_readlane(incl, WAVE - 1);
-    cr.T = (cr.N + (WAVE - 1)) >> 6;
-    cr.codable = mk_ballot(cr.len > (1u << SURV_OFF_BITS)) == 0ull;      // (run index < 64: 6 bits)
+    link_candidate_runs(cr);
     return cr;
 }
 
@@ -1610,8 +1624,53 @@ struct CandLoader {
     const unsigned* __restrict__ rec_cls;
 };
 
+// The place of a traversal in the runs, all of it wave-uniform (scalar registers): the runs still ahead, the end of the
+// current run and the two words that turn a candidate number of that run into its record index (n + rd) and its survivor
+// code (n + cd: the run's OWN index -- what for_each_survivor reads r0 by -- above the offset; the offset inside a codable
+// run is below 1 << SURV_OFF_BITS, so the sum is the code's `|`).  Starts in front of the first run.
+struct CandCursor {
+    unsigned long long ahead;
+    unsigned end, rd, cd;
+};
+
+MK_DEV CandCursor cand_cursor_begin(const CandRuns& cr)
+{
+    CandCursor cur;
+    cur.ahead = cr.held; cur.end = 0u; cur.rd = 0u; cur.cd = 0u;
+    return cur;
+}
+
+// on to the next run that holds records; it starts where the one before it ended.  Two v_readlane, the rest is scalar.
+MK_DEV void cand_cursor_step(const CandRuns& cr, CandCursor& cur)
+{
+    const int j = mk_ctz64(cur.ahead);
+    cur.ahead &= cur.ahead - 1ull;
+    const unsigned pre = cur.end;
+    cur.end = mk_readlane(cr.end, j);
+    cur.rd = mk_readlane(cr.r0, j) - pre;
+    cur.cd = ((unsigned)j << SURV_OFF_BITS) - pre;
+}
+
+// chunk [n0, n0 + 64), n0 < N, this lane's number n: record index and code of n (meaningless for a lane with n >= N).
+// The cursor first moves to the run that holds n0 -- a step at most, several behind runs shorter than a chunk (or
+// where chunks are left out: right, but a team's strided traversal does not use the cursor, see cand_issue) -- and a
+// chunk inside that run costs two adds.  Every further run that begins inside the chunk is claimed by the lanes at or behind its first number.
+MK_DEV void cand_cursor_seek(const CandRuns& cr, CandCursor& cur, unsigned n0, unsigned n, unsigned& r, unsigned& code)
+{
+    while (cur.end <= n0 && cur.ahead != 0ull) cand_cursor_step(cr, cur);         // wave-uniform
+    r = n + cur.rd;
+    code = n + cur.cd;
+    while (cur.end < n0 + (unsigned)WAVE && cur.ahead != 0ull) {                  // wave-uniform
+        const unsigned pre = cur.end;
+        cand_cursor_step(cr, cur);
+        const bool behind = n >= pre;
+        r = behind ? n + cur.rd : r;
+        code = behind ? n + cur.cd : code;
+    }
+}
+
 template <bool LOAD_CLS>
-MK_DEV void cand_issue(const CandLoader& L, unsigned t, CandChunk& ch)
+MK_DEV void cand_issue(const CandLoader& L, CandCursor& cur, bool strided, unsigned t, CandChunk& ch)
 {
     const CandRuns& cr = L.cr;
     const float4* __restrict__ rec_pos = L.rec_pos;
@@ -1621,18 +1680,27 @@ MK_DEV void cand_issue(const CandLoader& L, unsigned t, CandChunk& ch)
         ch.r = 0u; ch.valid = false; ch.ids = 0u; ch.code = 0u;
         ch.P = make_float4(0.f, 0.f, 0.f, 0.f);
         if (t < cr.T) {                                              // wave-uniform
-            // candidate numbers [64 t, 64 t + 64): the runs that overlap them (a handful), each claimed by its lanes
+            // candidate numbers [64 t, 64 t + 64)
             const unsigned n0 = t << 6, n = n0 + (unsigned)lane;
-            unsigned long long over = mk_ballot(cr.len != 0u && cr.pre < n0 + (unsigned)WAVE && cr.pre + cr.len > n0);
-            while (over) {                                           // wave-uniform
-                const int j = mk_ctz64(over);
-                over &= over - 1ull;
-                const unsigned pj = mk_readlane(cr.pre, j), lj = mk_readlane(cr.len, j), rj = mk_readlane(cr.r0, j);
-                const unsigned off = n - pj;
-                const bool mine = off < lj;                          // unsigned: pj <= n < pj + lj  (selects, not a branch:
-                ch.r = mine ? rj + off : ch.r;                       //  the masked-region form costs a dozen scalar ops per run)
-                ch.code = mine ? (((unsigned)j << SURV_OFF_BITS) | off) : ch.code;
-                ch.valid = ch.valid || mine;
+            if ((MK_AB & 2) || strided) {
+                // a team's wave takes every TEAM-th chunk and would have to step the cursor through every run between two of them,
+                // one dependent scalar step after the other, in a kernel that is bound by latency (measured: the one-grid call
+                // 40.4 -> 42.0 us): it searches the runs that overlap the chunk, each claimed by its lanes, as every traversal
+                // did before round 9 (MK_AB & 2: everywhere, the A-B of the cursor).  `strided` is a constant of the instance.
+                unsigned long long over = mk_ballot(cr.len != 0u && cr.pre < n0 + (unsigned)WAVE && cr.pre + cr.len > n0);
+                while (over) {                                       // wave-uniform
+                    const int j = mk_ctz64(over);
+                    over &= over - 1ull;
+                    const unsigned pj = mk_readlane(cr.pre, j), lj = mk_readlane(cr.len, j), rj = mk_readlane(cr.r0, j);
+                    const unsigned off = n - pj;
+                    const bool mine = off < lj;                      // unsigned: pj <= n < pj + lj
+                    ch.r = mine ? rj + off : ch.r;
+                    ch.code = mine ? (((unsigned)j << SURV_OFF_BITS) | off) : ch.code;
+                    ch.valid = ch.valid || mine;
+                }
+            } else {
+                ch.valid = n < cr.N;
+                cand_cursor_seek(cr, cur, n0, n, ch.r, ch.code);            // (r and code of a lane past N are never read)
             }
             if (ch.valid) {
                 ch.P = rec_pos[ch.r];
@@ -1675,10 +1743,11 @@ MK_DEV void for_each_candidate(const GridDesc& g, const TileGeom& tg, const Cand
     //  them in flight together; dealing whole batches left the 3PTB pocket's waves with 0 to 4 chunks each: 28.3 -> 25.9 us
     //  per call.  Six or eight in flight instead of four change nothing for a 64^3 grid's 24-chunk tiles)
     CandChunk ch[BATCH];
+    CandCursor cur = cand_cursor_begin(cr);                           // one per traversal, advanced in chunk order as the loads are issued
     for (unsigned t = first_batch; t < T; t += BATCH * batch_stride) {
         MK_PHASE_NOW(ta_);
 #pragma unroll
-        for (int k = 0; k < BATCH; ++k) cand_issue<LOAD_CLS>(ld, t + (unsigned)k * batch_stride, ch[k]);
+        for (int k = 0; k < BATCH; ++k) cand_issue<LOAD_CLS>(ld, cur, batch_stride != 1u, t + (unsigned)k * batch_stride, ch[k]);
         MK_PHASE_DRAIN();
         MK_PHASE_NOW(tb_);
 #pragma unroll
@@ -2045,6 +2114,17 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
         // ---- one channel, class by class: inner loop = sub, fma, half a min3 per (voxel, entry); the
         //      class flush applies the cutoff to the class minimum and scales by w ----
         auto process_classes = [&](int c, unsigned bits, unsigned (&acc)[KL]) {
+            // cover fold, once per channel: the COVERED classes of channel c go first.  Behind the last of them acc (= q[c], +inf
+            // at the start of every tile) is exactly the minimum of the flushed values these groups would have folded one by
+            // one, and a minimum of minima is the minimum -- one fold there, the same bits; the uncovered classes (the
+            // hydrogens) follow and fold nothing.  The order of the classes changes no value: acc and q[7] are minima, and the
+            // entries sit where the placement put them.  (MK_AB & 1: the fold per group as before, the A-B of this.)
+            const bool fold_here = !DENSE && c != CHG - 1 && !(MK_DIAG & (2 | 128));
+            const bool fold_once = fold_here && !(MK_AB & 1);
+            unsigned later = fold_once ? bits & ~(cover >> 1) : 0u;      // wave-uniform: the classes behind the fold
+            bits &= ~later;
+            bool fold_due = fold_once && bits != 0u;
+            if (bits == 0u) { bits = later; later = 0u; }
             while (bits) {                                                // wave-uniform
                 const int cls = __builtin_ctz(bits);
                 bits &= bits - 1u;
@@ -2137,11 +2217,17 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
                 }
                 // cover fold: channel 7 left these atoms out of its own lists (a team's wave folds its own partial flush)
                 if constexpr (!DENSE) {
-                    if (c != CHG - 1 && ((cover >> (cls + 1)) & 1u) != 0u && !(MK_DIAG & (2 | 128))) {      // wave-uniform
+                    if (fold_here && !fold_once && ((cover >> (cls + 1)) & 1u) != 0u) {                   // wave-uniform
 #pragma unroll
                         for (int k = 0; k < KL; ++k) q[CHG - 1][k] = mk_min_bits(q[CHG - 1][k], m[k]);
                     }
+                    if (bits == 0u && fold_due) {                         // wave-uniform: the last covered class of the channel is flushed
+#pragma unroll
+                        for (int k = 0; k < KL; ++k) q[CHG - 1][k] = mk_min_bits(q[CHG - 1][k], mk_uint_as_float(acc[k]));
+                        fold_due = false;
+                    }
                 }
+                if (bits == 0u) { bits = later; later = 0u; }
             }
         };
         // dense tiles only: a finished channel goes straight to memory (4-byte stores, 32-byte stride)
