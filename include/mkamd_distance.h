@@ -422,6 +422,35 @@ int mkamd_hbonds_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int6
  * per chunk instead of what a 256 MB workspace allows (0: default, a multiple of 64).  Every plan produces the same list. */
 int mkamd_ctx_set_hbond_plan(mkamd_ctx* ctx, int avoid_mask, int64_t chunk_frames);
 
+/* ---- bond guesser of one frame (moleculekit bondguesser.py: `bond_grid_search`; bondguesser_utils.pyx: the pair test) ----
+ *   coords float32 [n_atoms, 3]   one frame, atom-major; must be finite
+ *   radii float32 [n_atoms]       the atoms' radii (bondguesser.py's table, the defaults by atom name, 1.5: the caller's)
+ *   is_hydrogen uint32 [n_atoms]  != 0: a hydrogen; two hydrogens never bond
+ *   grid_cutoff, max_boxes, cutoff_incr   `bond_grid_search`'s (its defaults: 4e6, 1.26): the box side starts at grid_cutoff and is
+ *                                 multiplied by cutoff_incr, in double, while the grid has more than max_boxes boxes
+ * The grid is the reference's non-periodic one: per-axis float32 minimum, floor(range / float32(box side)) + 1 boxes an axis, an atom's
+ * box floor((x - min) / float32(box side)) clipped to the grid -- float32 subtractions and correctly rounded float32 divisions.  A pair
+ * of neighbouring boxes' atoms bonds where dist2 = (dx dx + dy dy) + dz dz (every float32 operation rounded on its own) is neither
+ * above float32(box side)^2 nor, widened to double, below 0.001, and not above float32(0.6 * double(r_i + r_j))^2.
+ * Result: *n rows of *pairs, int32 [n, 2] = (i, j) in the REFERENCE'S ORDER (occupied boxes by their lowest atom; owners ascending; its
+ * 14 neighbour relations in its order; partners ascending; rows not sorted within themselves).  The list is context-owned (NULL when
+ * n = 0) and valid until the next bond call on the context.  grid (may be NULL) double [4]: boxes per axis and the box side the call
+ * settled on.
+ * A box may hold at most 4 096 atoms (the cell list's sort and the pair kernels are quadratic in a box's atoms): a frame that puts more
+ * into one box -- coincident atoms -- ends the call with MKAMD_EINVAL and a message naming the box and its occupancy.
+ * Not asynchronous: the bounds, the occupancies and the size of the list reach the host on the way.
+ * MKAMD_EINVAL: a non-finite coordinate; a grid_cutoff that is not positive and finite; max_boxes outside [1, 2^28]; cutoff_incr <= 1;
+ * n_atoms >= 2^31; a box over the cap; more than 2^31 bonds.
+ * _dev: the three arrays are device pointers and the list is device memory. */
+int mkamd_guess_bonds_dev(mkamd_ctx* ctx, const float* d_coords, const float* d_radii, const uint32_t* d_is_hydrogen, int64_t n_atoms,
+                          double grid_cutoff, double max_boxes, double cutoff_incr, int64_t* n, const int32_t** d_pairs, double* grid);
+/* host arrays; the list is host memory */
+int mkamd_guess_bonds_host(mkamd_ctx* ctx, const float* coords, const float* radii, const uint32_t* is_hydrogen, int64_t n_atoms,
+                           double grid_cutoff, double max_boxes, double cutoff_incr, int64_t* n, const int32_t** pairs, double* grid);
+/* The launch plan of the bond calls (tests, same-box A-B timing).  avoid_mask: 1 not the pair kernels with a thread per owner, 2 not
+ * those with a wave per owner (default 0: a wave per owner where some box holds 64 atoms or more).  Both produce the same list. */
+int mkamd_ctx_set_bond_plan(mkamd_ctx* ctx, int avoid_mask);
+
 #ifdef __cplusplus
 }
 #endif

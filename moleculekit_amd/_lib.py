@@ -156,6 +156,10 @@ SIGNATURES = {
     "mkamd_hbonds_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _c_int, _c_int,
                                    _vp, ctypes.POINTER(_vp)]),
     "mkamd_ctx_set_hbond_plan": (_c_int, [_vp, _c_int, _c_i64]),
+    # include/mkamd_distance.h, bond guesser
+    "mkamd_guess_bonds_dev": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _c_dbl, ctypes.POINTER(_c_i64), ctypes.POINTER(_vp), _vp]),
+    "mkamd_guess_bonds_host": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _c_dbl, ctypes.POINTER(_c_i64), ctypes.POINTER(_vp), _vp]),
+    "mkamd_ctx_set_bond_plan": (_c_int, [_vp, _c_int]),
 }
 
 # operations of mkamd_selftest_arith (csrc/arith_probe.h): name -> (code, arrays read, their dtype, result dtype, results per element)
@@ -439,6 +443,11 @@ class Context:
         kernels; ``chunk_frames`` > 0 forces the frames per chunk.  Every plan produces the same list (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_hbond_plan(self._h, int(avoid_mask), int(chunk_frames)))
 
+    def set_bond_plan(self, avoid_mask: int = 0):
+        """The launch plan of the bond calls (include/mkamd_distance.h): avoid 1 the pair kernels with a thread per owner, 2 those with
+        a wave per owner.  Both produce the same list (tests, A-B timing)."""
+        _check(load().mkamd_ctx_set_bond_plan(self._h, int(avoid_mask)))
+
     def set_reduction_block(self, block: int = 0):
         """0: choose; 4 / 8: first-group atoms a wave of the closest-atom group reduction keeps in registers; -1: the generic kernel."""
         _check(load().mkamd_ctx_set_reduction_block(self._h, int(block)))
@@ -623,6 +632,25 @@ class Context:
                                        float(dist_threshold), float(angle_threshold), int(bool(intra)), int(bool(ignore_hs)), _ptr(offs),
                                        ctypes.byref(pt)))
         return offs, int(pt.value or 0), int(offs[-1])
+
+    def guess_bonds_host(self, coords, radii, is_hydrogen, grid_cutoff, max_boxes=4e6, cutoff_incr=1.26):
+        """float32 [N, 3], float32 [N], uint32 [N] -> (pairs int32 [n, 2], (nx, ny, nz, box side)) -- found and ordered on the GPU."""
+        n, pp, grid = _c_i64(0), _vp(None), np.zeros(4, dtype=np.float64)
+        _check(load().mkamd_guess_bonds_host(self._h, _ptr(coords), _ptr(radii), _ptr(is_hydrogen), coords.shape[0], float(grid_cutoff),
+                                             float(max_boxes), float(cutoff_incr), ctypes.byref(n), ctypes.byref(pp), _ptr(grid)))
+        grid = (int(grid[0]), int(grid[1]), int(grid[2]), float(grid[3]))
+        k = int(n.value)
+        if k == 0 or not pp.value:
+            return np.zeros((0, 2), dtype=np.int32), grid
+        return np.frombuffer((ctypes.c_int32 * (2 * k)).from_address(pp.value), dtype=np.int32).reshape(k, 2).copy(), grid   # context-owned: copied
+
+    def guess_bonds_dev(self, d_coords, d_radii, d_is_hydrogen, N, grid_cutoff, max_boxes=4e6, cutoff_incr=1.26):
+        """the three arrays on the device -> (address of the device list of 2 n int32 (context-owned until the next bond call; 0 when
+        empty), n, (nx, ny, nz, box side))."""
+        n, pp, grid = _c_i64(0), _vp(None), np.zeros(4, dtype=np.float64)
+        _check(load().mkamd_guess_bonds_dev(self._h, _ptr(d_coords), _ptr(d_radii), _ptr(d_is_hydrogen), N, float(grid_cutoff), float(max_boxes),
+                                            float(cutoff_incr), ctypes.byref(n), ctypes.byref(pp), _ptr(grid)))
+        return int(pp.value or 0), int(n.value), (int(grid[0]), int(grid[1]), int(grid[2]), float(grid[3]))
 
     def dist_reduction_dev(self, d_coords, N, F, d_box, d_g1a, d_g1o, ng1, n_g1_atoms, d_g2a, d_g2o, ng2, d_ch1, d_ch2, selfdist, pairs, pbc,
                            d_masses, r1, r2, d_out):

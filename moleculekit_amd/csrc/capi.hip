@@ -18,6 +18,7 @@
 #include "wrap_cell_pipeline.h"
 #include "ring_pipeline.h"
 #include "hbond_pipeline.h"
+#include "bond_pipeline.h"
 #include "arith_probe.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
@@ -122,6 +123,8 @@ struct mkamd_ctx {
     std::vector<int> hbond_triples_host;   // result of the last mkamd_hbonds_host call (owned here)
     int hbond_avoid = 0;                   // mkamd_ctx_set_hbond_plan
     long long hbond_chunk = 0;
+    std::vector<int> bond_pairs_host;      // result of the last mkamd_guess_bonds_host call (owned here)
+    int bond_avoid = 0;                    // mkamd_ctx_set_bond_plan
     std::vector<float> packed_coords;      // the selected atoms' rows of a host distance call (host_pack.h), kept between calls
     std::vector<float> f32_stage;          // host staging of big float64-out results
     struct PendingHostCall { bool active = false; size_t out_bytes = 0; bool mapped_out = false; unsigned seq = 0; void* dout = nullptr; hipEvent_t done = nullptr; };
@@ -2423,6 +2426,82 @@ try {
                            mkamd::HbondHostSink<mkamd_ctx>{*ctx, ctx->hbond_triples_host}, err, ctx->hbond_avoid);
     if (st) return run_status(st, err);
     if (!ctx->hbond_triples_host.empty()) *triples = ctx->hbond_triples_host.data();
+    return MKAMD_OK;
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// bond guesser (include/mkamd_distance.h "bond guesser"; bond_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_ctx_set_bond_plan(mkamd_ctx* ctx, int avoid_mask)
+try {
+    if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
+    if (avoid_mask < 0 || avoid_mask > 2) return fail(MKAMD_EINVAL, "bond plan: avoid mask 0, 1 (not a thread per owner) or 2 (not a wave per owner)");
+    ctx->bond_avoid = avoid_mask;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+static int guess_bonds_impl(mkamd_ctx* ctx, const float* d_coords, const float* d_radii, const uint32_t* d_is_h, int64_t n_atoms, double grid_cutoff,
+                            double max_boxes, double cutoff_incr, mkamd::BondResult& R, double* grid)
+{
+    mkamd::BondArgs a;
+    a.coords = d_coords; a.radii = d_radii; a.is_h = d_is_h; a.n = n_atoms;
+    a.grid_cutoff = grid_cutoff; a.max_boxes = max_boxes; a.cutoff_incr = cutoff_incr;
+    std::string err;
+    const int st = mkamd::run_guess_bonds(*ctx, a, R, err, ctx->bond_avoid);
+    if (grid) {
+        for (int ax = 0; ax < 3; ++ax) grid[ax] = (double)R.boxes[ax];
+        grid[3] = R.pairdist;
+    }
+    return run_status(st, err);
+}
+
+extern "C" int mkamd_guess_bonds_dev(mkamd_ctx* ctx, const float* d_coords, const float* d_radii, const uint32_t* d_is_hydrogen, int64_t n_atoms,
+                                     double grid_cutoff, double max_boxes, double cutoff_incr, int64_t* n, const int32_t** d_pairs, double* grid)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (!n || !d_pairs) return fail(MKAMD_EINVAL, "n / d_pairs pointer is NULL");
+    *n = 0;
+    *d_pairs = nullptr;
+    static_assert(sizeof(int) == sizeof(int32_t) && sizeof(unsigned) == sizeof(uint32_t), "the list is int32, the flags uint32");
+    mkamd::BondResult R;
+    if ((st = guess_bonds_impl(ctx, d_coords, d_radii, d_is_hydrogen, n_atoms, grid_cutoff, max_boxes, cutoff_incr, R, grid))) return st;
+    *n = R.n_pairs;
+    if (R.n_pairs) *d_pairs = R.pairs;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_guess_bonds_host(mkamd_ctx* ctx, const float* coords, const float* radii, const uint32_t* is_hydrogen, int64_t n_atoms,
+                                      double grid_cutoff, double max_boxes, double cutoff_incr, int64_t* n, const int32_t** pairs, double* grid)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (!n || !pairs) return fail(MKAMD_EINVAL, "n / pairs pointer is NULL");
+    *n = 0;
+    *pairs = nullptr;
+    ctx->bond_pairs_host.clear();
+    if (n_atoms < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (n_atoms >= 0x80000000LL) return fail(MKAMD_EINVAL, "too many atoms (>= 2^31)");
+    if (n_atoms > 0 && (!coords || !radii || !is_hydrogen)) return fail(MKAMD_EINVAL, "NULL pointer");
+    void *dc = nullptr, *dr = nullptr, *dh = nullptr;
+    if (n_atoms > 0) {
+        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)n_atoms * 12, &dc)) || (st = upload(ctx, WS_H_SIGMAS, radii, (size_t)n_atoms * 4, &dr)) ||
+            (st = upload(ctx, WS_H_OFFSETS, is_hydrogen, (size_t)n_atoms * 4, &dh)))
+            return st;
+    }
+    mkamd::BondResult R;
+    if ((st = guess_bonds_impl(ctx, (const float*)dc, (const float*)dr, (const uint32_t*)dh, n_atoms, grid_cutoff, max_boxes, cutoff_incr, R, grid))) {
+        (void)hipStreamSynchronize(ctx->stream);                      // (the uploads read the caller's arrays)
+        return st;
+    }
+    if (R.n_pairs) {
+        ctx->bond_pairs_host.resize((size_t)R.n_pairs * 2);
+        if ((st = ctx->to_host(ctx->bond_pairs_host.data(), R.pairs, (size_t)R.n_pairs * 8))) return st;
+        *pairs = ctx->bond_pairs_host.data();
+    } else {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    *n = R.n_pairs;
     return MKAMD_OK;
 } MK_API_CATCH
 

@@ -56,6 +56,8 @@ enum WsSlot {
     WS_R_EMIT, WS_R_OUT2,
     // hydrogen bonds (hbond_pipeline.h): the call's table (rows, sublists, tile numbering); the chunk's masks and counters; the context-owned list
     WS_HB_TABLE, WS_HB_MASK, WS_HB_CNT, WS_HB_TOT, WS_HB_BASE, WS_HB_TRIPLES,
+    // bond guesser (bond_pipeline.h): status words; its scans' chunk sums; two words per box; the per-atom arrays; the context-owned list
+    WS_BD_STAT, WS_BD_CHUNKS, WS_BD_BOXCNT, WS_BD_BOXLOW, WS_BD_ATOMBOX, WS_BD_A, WS_BD_B, WS_BD_START, WS_BD_TMP, WS_BD_ORDER, WS_BD_PAIRS,
     WS_NSLOTS
 };
 

@@ -461,13 +461,23 @@ def _select(mol, sel, N, guess_bonds):
     return np.where(a < 0, a + N, a).astype(_U32)
 
 
+def _all_bonds(mol, file_bonds, fileBonds, ctx=None):
+    """the reference's ``_getBonds(fileBonds, True)``: the file bonds, if wanted, on top of the bonds guessed on the device"""
+    from . import bonds as _bonds
+
+    guessed = _bonds.guess_bonds(mol, ctx=ctx)
+    return np.vstack((file_bonds.astype(_U32), guessed)) if fileBonds else guessed
+
+
 def wrap_molecule(mol, wrapsel="all", fileBonds=True, guessBonds=False, wrapcenter=None, unitcell="rectangular", ctx=None, *,
-                  triclinic_on_device=False):
+                  triclinic_on_device=False, guess_on_device=False):
     """The reference's ``Molecule.wrap`` on the GPU: ``mol.coords`` (float32 ``[N, 3, F]``) is wrapped in place around the atoms
     ``wrapsel`` (a mask or an index array; ``"all"``) or around ``wrapcenter``, by the bonded groups of ``mol.bonds``
     (``fileBonds=False``: every atom on its own).  As the reference: ``ValueError`` for an unknown ``unitcell``, a warning and no
     change when the whole box is zero, ``RuntimeError`` when box and coordinates differ in their number of frames.  Unlike it:
-    ``guessBonds=True`` raises ``NotImplementedError``, a bonded group that is not contiguous raises ``ValueError``, and a triclinic
+    ``guessBonds=True`` raises ``NotImplementedError`` unless ``guess_on_device=True`` -- then the groups are those of the reference's
+    ``_getBonds(fileBonds, guessBonds)``: the file bonds (if ``fileBonds``) stacked on top of ``bonds.guess_bonds(mol)``, the bonds of
+    frame ``mol.frame`` guessed on the device --, a bonded group that is not contiguous raises ``ValueError``, and a triclinic
     box (any ``boxangles`` other than 90 in any frame) raises ``NotImplementedError`` unless ``triclinic_on_device=True``: then, as in
     the reference, the whole call takes ``wrap_cell`` with ``box_vectors(mol.box, mol.boxangles)`` and ``unitcell`` ("rectangular",
     "triclinic" or "compact"); a box whose angles are all 90 takes ``wrap`` whatever ``unitcell`` says."""
@@ -497,14 +507,14 @@ def wrap_molecule(mol, wrapsel="all", fileBonds=True, guessBonds=False, wrapcent
         return
     if box.shape[1] != coords.shape[2]:
         raise RuntimeError(_FRAMES)
-    if guessBonds:
+    if guessBonds and not guess_on_device:
         raise NotImplementedError("guessBonds=True: this package does not guess bonds; pass a molecule whose bonds are read from a topology")
     angles = getattr(mol, "boxangles", None)
     triclinic = angles is not None and np.size(angles) and bool(np.any(np.asarray(angles) != 90))
     if triclinic and not triclinic_on_device:
         raise NotImplementedError("the box is triclinic (boxangles != 90): the unit cells 'rectangular', 'triclinic' and 'compact' of a "
                                   "triclinic box are not wrapped on the device; use the reference's Molecule.wrap")
-    groups = bonded_groups(bonds if fileBonds else None, N)
+    groups = bonded_groups(_all_bonds(mol, bonds, fileBonds, ctx) if guessBonds else (bonds if fileBonds else None), N)
     if triclinic:
         mol.coords[...] = wrap_cell(np.ascontiguousarray(coords, dtype=_F32), box_vectors(box, angles), groups, unitcell,
                                     centersel=centersel if center is None else None, center=center, ctx=ctx)
@@ -514,17 +524,21 @@ def wrap_molecule(mol, wrapsel="all", fileBonds=True, guessBonds=False, wrapcent
 
 
 def _molecule_wrap(self, wrapsel="all", fileBonds=True, guessBonds=False, wrapcenter=None, unitcell="rectangular"):
-    """``Molecule.wrap`` once ``install()``-ed: the device for rectangular boxes and, after ``install(triclinic=True)``, triclinic ones;
-    the saved original for guessed bonds, bonded groups that are not contiguous and (by default) triclinic boxes"""
+    """``Molecule.wrap`` once ``install()``-ed: the device for rectangular boxes and, after ``install(triclinic=True)``, triclinic ones
+    and, after ``install(guess=True)``, guessed bonds; the saved original for bonded groups that are not contiguous and (by default)
+    guessed bonds and triclinic boxes"""
     import moleculekit.molecule as ref
 
     original = ref._mkamd_reference_wrap
     angles = getattr(self, "boxangles", None)
     on_device = bool(getattr(ref, "_mkamd_wrap_triclinic", False))
     triclinic = angles is not None and np.size(angles) and np.any(np.asarray(angles) != 90) and not on_device
-    if guessBonds or triclinic or not isinstance(unitcell, str) or unitcell.lower() not in UNITCELLS:
+    guess = bool(getattr(ref, "_mkamd_wrap_guess", False))
+    if (guessBonds and not guess) or triclinic or not isinstance(unitcell, str) or unitcell.lower() not in UNITCELLS:
         return original(self, wrapsel, fileBonds, guessBonds, wrapcenter, unitcell)
     try:
+        if guessBonds:
+            return wrap_molecule(self, wrapsel, fileBonds, guessBonds, wrapcenter, unitcell, triclinic_on_device=on_device, guess_on_device=True)
         if fileBonds:
             bonded_groups(self.bonds, int(np.asarray(self.coords).shape[0]))
     except NonContiguousGroups:
@@ -532,15 +546,17 @@ def _molecule_wrap(self, wrapsel="all", fileBonds=True, guessBonds=False, wrapce
     return wrap_molecule(self, wrapsel, fileBonds, guessBonds, wrapcenter, unitcell, triclinic_on_device=on_device)
 
 
-def install(triclinic=False):
+def install(triclinic=False, guess=False):
     """Swap ``Molecule.wrap`` of an installed moleculekit for the GPU's: the reference's own projections (``mol.wrap(centersel)``,
     then ``mol.align(...)``) and everything else built on ``Molecule.wrap`` then wrap on the device.  ``guessBonds=True`` and
     molecules whose bonded groups are not contiguous go to the saved original, and so do triclinic boxes unless ``triclinic=True``
-    (the last call's value holds).  Returns the original; idempotent; ``uninstall()`` puts it back and clears the flag.  Independent of
-    the other ``install()`` hooks."""
+    (the last call's value holds).  ``guess=True`` keeps ``guessBonds=True`` calls on the device too (``bonds.guess_bonds``); they fall
+    back to the original only where the groups are not contiguous (the last call's value holds).  Returns the original; idempotent;
+    ``uninstall()`` puts it back and clears the flags.  Independent of the other ``install()`` hooks."""
     import moleculekit.molecule as ref
 
     ref._mkamd_wrap_triclinic = bool(triclinic)
+    ref._mkamd_wrap_guess = bool(guess)
     saved = getattr(ref, "_mkamd_reference_wrap", None)
     if saved is not None:
         return saved
@@ -556,6 +572,7 @@ def uninstall():
 
     saved = getattr(ref, "_mkamd_reference_wrap", None)
     ref._mkamd_wrap_triclinic = False
+    ref._mkamd_wrap_guess = False
     if saved is not None:
         ref.Molecule.wrap = saved
         ref._mkamd_reference_wrap = None
