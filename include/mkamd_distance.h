@@ -451,6 +451,42 @@ int mkamd_guess_bonds_host(mkamd_ctx* ctx, const float* coords, const float* rad
  * those with a wave per owner (default 0: a wave per owner where some box holds 64 atoms or more).  Both produce the same list. */
 int mkamd_ctx_set_bond_plan(mkamd_ctx* ctx, int avoid_mask);
 
+/* ---- steric clashes of one frame (moleculekit distance.py: `find_clashes`) ----
+ *   coords float32 [n_atoms, 3]   one frame, atom-major; the selected atoms' must be finite
+ *   radii float32 [n_atoms]       the atoms' van der Waals radii (the caller's: the reference's table, 1.7 where it has none)
+ *   sel1, sel2 uint32 [n_atoms]   != 0: the atom is in the first / second selection.  self_mode != 0: one selection (sel2 is not read)
+ *                                 and rows a < b; otherwise ordered rows (a of sel1, b of sel2) with no such filter, so selections that
+ *                                 overlap yield (a, b), (b, a) and (a, a)
+ *   ex_start uint32 [n_atoms + 1], ex_partner uint32 [ex_start[n_atoms]]   the exclusion table, or both NULL: row a holds, ascending,
+ *                                 the partners b >= a with which (a, b) is excluded.  A row (a, b) with a > b is never looked up (the
+ *                                 reference looks rows up as found in a set of (min, max) tuples).  The _dev call trusts the table
+ *   overlap                       a clash where dist < float32(float32(r_a + r_b) - float32(overlap)), strictly
+ *   cutoff                        the reference's kd-tree radius, 2 max(radii) - overlap over ALL atoms, in double: a row also needs
+ *                                 (dx dx + dy dy) + dz dz <= cutoff * cutoff in float64 on the widened coordinates (the kd-tree squares
+ *                                 its radius: a negative cutoff searches like its absolute value)
+ *   max_boxes                     the cell list's grid holds at most this many boxes (in [1, 2^28]); the box side is at least |cutoff|
+ * dist = the correctly rounded float32 root of (dx dx + dy dy) + dz dz, every float32 operation rounded on its own; the row's overlap is
+ * float32(float32(r_a + r_b) - dist).
+ * Result: *n rows of *pairs int32 [n, 2] = (a, b), *dist float32 [n], *overlap float32 [n].  The lists are context-owned (NULL when
+ * n = 0) and valid until the next clash call on the context.  info (may be NULL) double [6]: boxes per axis, the box side, the atoms of
+ * the most crowded box, the owners (selected atoms of sel1).
+ * _dev: every array is a device pointer, the lists are device memory, and the rows come in the pair kernels' order (owners in cell order,
+ * the 27 boxes around each, partners ascending within a box): the same on every run and under both plans; the caller sorts.
+ * _host: host arrays, the lists are host memory, sorted by overlap, largest first, equal overlaps by (a, b) ascending; the table is checked.
+ * A box may hold at most 4 096 atoms: a frame that puts more into one ends the call with MKAMD_EINVAL and a message naming the box.
+ * Not asynchronous.  MKAMD_EINVAL: a non-finite coordinate in a selection; overlap or cutoff not finite; max_boxes outside [1, 2^28];
+ * n_atoms >= 2^31; a box over the cap; more than 2^31 rows; (_host) a table that is not a CSR of ascending rows over n_atoms atoms. */
+int mkamd_find_clashes_dev(mkamd_ctx* ctx, const float* d_coords, const float* d_radii, const uint32_t* d_sel1, const uint32_t* d_sel2,
+                           int64_t n_atoms, int self_mode, const uint32_t* d_ex_start, const uint32_t* d_ex_partner, double overlap, double cutoff,
+                           double max_boxes, int64_t* n, const int32_t** d_pairs, const float** d_dist, const float** d_overlap, double* info);
+int mkamd_find_clashes_host(mkamd_ctx* ctx, const float* coords, const float* radii, const uint32_t* sel1, const uint32_t* sel2, int64_t n_atoms,
+                            int self_mode, const uint32_t* ex_start, const uint32_t* ex_partner, double overlap, double cutoff, double max_boxes,
+                            int64_t* n, const int32_t** pairs, const float** dist, const float** overlap_out, double* info);
+/* The launch plan of the clash calls (tests, same-box A-B timing).  avoid_mask: 1 not the pair kernels with a thread per owner, 2 not
+ * those with a wave per owner (default 0: a wave per owner while the owners number at most 8 192 or some box holds 64 atoms or more).
+ * Both produce the same rows in the same order. */
+int mkamd_ctx_set_clash_plan(mkamd_ctx* ctx, int avoid_mask);
+
 #ifdef __cplusplus
 }
 #endif

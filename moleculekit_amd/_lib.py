@@ -160,6 +160,12 @@ SIGNATURES = {
     "mkamd_guess_bonds_dev": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _c_dbl, ctypes.POINTER(_c_i64), ctypes.POINTER(_vp), _vp]),
     "mkamd_guess_bonds_host": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _c_dbl, ctypes.POINTER(_c_i64), ctypes.POINTER(_vp), _vp]),
     "mkamd_ctx_set_bond_plan": (_c_int, [_vp, _c_int]),
+    # include/mkamd_distance.h, steric clashes
+    "mkamd_find_clashes_dev": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _c_dbl, _c_dbl, ctypes.POINTER(_c_i64),
+                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "mkamd_find_clashes_host": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _c_dbl, _c_dbl, ctypes.POINTER(_c_i64),
+                                         ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "mkamd_ctx_set_clash_plan": (_c_int, [_vp, _c_int]),
 }
 
 # operations of mkamd_selftest_arith (csrc/arith_probe.h): name -> (code, arrays read, their dtype, result dtype, results per element)
@@ -448,6 +454,11 @@ class Context:
         a wave per owner.  Both produce the same list (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_bond_plan(self._h, int(avoid_mask)))
 
+    def set_clash_plan(self, avoid_mask: int = 0):
+        """The launch plan of the clash calls (include/mkamd_distance.h): avoid 1 the pair kernels with a thread per owner, 2 those with
+        a wave per owner.  Both produce the same rows (tests, A-B timing)."""
+        _check(load().mkamd_ctx_set_clash_plan(self._h, int(avoid_mask)))
+
     def set_reduction_block(self, block: int = 0):
         """0: choose; 4 / 8: first-group atoms a wave of the closest-atom group reduction keeps in registers; -1: the generic kernel."""
         _check(load().mkamd_ctx_set_reduction_block(self._h, int(block)))
@@ -643,6 +654,32 @@ class Context:
         if k == 0 or not pp.value:
             return np.zeros((0, 2), dtype=np.int32), grid
         return np.frombuffer((ctypes.c_int32 * (2 * k)).from_address(pp.value), dtype=np.int32).reshape(k, 2).copy(), grid   # context-owned: copied
+
+    def _find_clashes(self, fn, coords, radii, sel1, sel2, N, ex_start, ex_partner, overlap, cutoff, max_boxes):
+        n, pp, pd, po, info = _c_i64(0), _vp(None), _vp(None), _vp(None), np.zeros(6, dtype=np.float64)
+        if isinstance(ex_partner, np.ndarray) and ex_partner.size == 0:
+            ex_partner = np.zeros(1, dtype=np.uint32)                 # an empty table still has an address
+        _check(fn(self._h, _ptr(coords), _ptr(radii), _ptr(sel1), _ptr(sel2), N, int(sel2 is None), _ptr(ex_start), _ptr(ex_partner), float(overlap),
+                  float(cutoff), float(max_boxes), ctypes.byref(n), ctypes.byref(pp), ctypes.byref(pd), ctypes.byref(po), _ptr(info)))
+        return int(n.value), int(pp.value or 0), int(pd.value or 0), int(po.value or 0), info
+
+    def find_clashes_host(self, coords, radii, sel1, sel2, ex_start, ex_partner, overlap, cutoff, max_boxes=4e6):
+        """float32 [N, 3], float32 [N], uint32 [N] masks (``sel2`` None: self mode), the exclusion CSR (uint32; both None: none) ->
+        (pairs int32 [n, 2], distances float32 [n], overlaps float32 [n], info) -- found on the GPU, sorted by overlap, largest first."""
+        k, pp, pd, po, info = self._find_clashes(load().mkamd_find_clashes_host, coords, radii, sel1, sel2, coords.shape[0], ex_start, ex_partner,
+                                                 overlap, cutoff, max_boxes)
+        if k == 0:
+            return np.zeros((0, 2), dtype=np.int32), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.float32), info
+        pairs = np.frombuffer((ctypes.c_int32 * (2 * k)).from_address(pp), dtype=np.int32).reshape(k, 2).copy()
+        dist = np.frombuffer((ctypes.c_float * k).from_address(pd), dtype=np.float32).copy()
+        over = np.frombuffer((ctypes.c_float * k).from_address(po), dtype=np.float32).copy()
+        return pairs, dist, over, info
+
+    def find_clashes_dev(self, d_coords, d_radii, d_sel1, d_sel2, N, d_ex_start, d_ex_partner, overlap, cutoff, max_boxes=4e6):
+        """every array on the device -> (n, addresses of the device lists of 2 n int32, n float32, n float32 (context-owned until the next
+        clash call; 0 when empty), info) -- the rows in the pair kernels' order."""
+        return self._find_clashes(load().mkamd_find_clashes_dev, d_coords, d_radii, d_sel1, d_sel2, N, d_ex_start, d_ex_partner, overlap, cutoff,
+                                  max_boxes)
 
     def guess_bonds_dev(self, d_coords, d_radii, d_is_hydrogen, N, grid_cutoff, max_boxes=4e6, cutoff_incr=1.26):
         """the three arrays on the device -> (address of the device list of 2 n int32 (context-owned until the next bond call; 0 when

@@ -19,6 +19,7 @@
 #include "ring_pipeline.h"
 #include "hbond_pipeline.h"
 #include "bond_pipeline.h"
+#include "clash_pipeline.h"
 #include "arith_probe.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
@@ -125,6 +126,9 @@ struct mkamd_ctx {
     long long hbond_chunk = 0;
     std::vector<int> bond_pairs_host;      // result of the last mkamd_guess_bonds_host call (owned here)
     int bond_avoid = 0;                    // mkamd_ctx_set_bond_plan
+    std::vector<int> clash_pairs_host;     // results of the last mkamd_find_clashes_host call (owned here)
+    std::vector<float> clash_dist_host, clash_over_host;
+    int clash_avoid = 0;                   // mkamd_ctx_set_clash_plan
     std::vector<float> packed_coords;      // the selected atoms' rows of a host distance call (host_pack.h), kept between calls
     std::vector<float> f32_stage;          // host staging of big float64-out results
     struct PendingHostCall { bool active = false; size_t out_bytes = 0; bool mapped_out = false; unsigned seq = 0; void* dout = nullptr; hipEvent_t done = nullptr; };
@@ -2498,6 +2502,123 @@ try {
         ctx->bond_pairs_host.resize((size_t)R.n_pairs * 2);
         if ((st = ctx->to_host(ctx->bond_pairs_host.data(), R.pairs, (size_t)R.n_pairs * 8))) return st;
         *pairs = ctx->bond_pairs_host.data();
+    } else {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    *n = R.n_pairs;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// steric clashes (include/mkamd_distance.h "steric clashes"; clash_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_ctx_set_clash_plan(mkamd_ctx* ctx, int avoid_mask)
+try {
+    if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
+    if (avoid_mask < 0 || avoid_mask > 2) return fail(MKAMD_EINVAL, "clash plan: avoid mask 0, 1 (not a thread per owner) or 2 (not a wave per owner)");
+    ctx->clash_avoid = avoid_mask;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+static int find_clashes_impl(mkamd_ctx* ctx, const float* d_coords, const float* d_radii, const uint32_t* d_sel1, const uint32_t* d_sel2, int64_t n_atoms,
+                             int self_mode, const uint32_t* d_ex_start, const uint32_t* d_ex_partner, double overlap, double cutoff, double max_boxes,
+                             mkamd::ClashResult& R, double* info)
+{
+    mkamd::ClashArgs a;
+    a.coords = d_coords; a.radii = d_radii; a.sel1 = d_sel1; a.sel2 = d_sel2; a.n = n_atoms; a.self_mode = self_mode ? 1 : 0;
+    a.ex_start = d_ex_start; a.ex_partner = d_ex_partner;
+    a.overlap = overlap; a.cutoff = cutoff; a.max_boxes = max_boxes;
+    std::string err;
+    const int st = mkamd::run_find_clashes(*ctx, a, R, err, ctx->clash_avoid);
+    if (info) {
+        for (int ax = 0; ax < 3; ++ax) info[ax] = (double)R.boxes[ax];
+        info[3] = R.side;
+        info[4] = (double)R.max_occ;
+        info[5] = (double)R.n_owners;
+    }
+    return run_status(st, err);
+}
+
+extern "C" int mkamd_find_clashes_dev(mkamd_ctx* ctx, const float* d_coords, const float* d_radii, const uint32_t* d_sel1, const uint32_t* d_sel2,
+                                      int64_t n_atoms, int self_mode, const uint32_t* d_ex_start, const uint32_t* d_ex_partner, double overlap,
+                                      double cutoff, double max_boxes, int64_t* n, const int32_t** d_pairs, const float** d_dist,
+                                      const float** d_overlap, double* info)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (!n || !d_pairs || !d_dist || !d_overlap) return fail(MKAMD_EINVAL, "n / d_pairs / d_dist / d_overlap pointer is NULL");
+    *n = 0;
+    *d_pairs = nullptr; *d_dist = nullptr; *d_overlap = nullptr;
+    mkamd::ClashResult R;
+    if ((st = find_clashes_impl(ctx, d_coords, d_radii, d_sel1, d_sel2, n_atoms, self_mode, d_ex_start, d_ex_partner, overlap, cutoff, max_boxes, R, info)))
+        return st;
+    *n = R.n_pairs;
+    if (R.n_pairs) { *d_pairs = R.pairs; *d_dist = R.dists; *d_overlap = R.overs; }
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_find_clashes_host(mkamd_ctx* ctx, const float* coords, const float* radii, const uint32_t* sel1, const uint32_t* sel2, int64_t n_atoms,
+                                       int self_mode, const uint32_t* ex_start, const uint32_t* ex_partner, double overlap, double cutoff,
+                                       double max_boxes, int64_t* n, const int32_t** pairs, const float** dist, const float** overlap_out, double* info)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (!n || !pairs || !dist || !overlap_out) return fail(MKAMD_EINVAL, "n / pairs / dist / overlap pointer is NULL");
+    *n = 0;
+    *pairs = nullptr; *dist = nullptr; *overlap_out = nullptr;
+    ctx->clash_pairs_host.clear(); ctx->clash_dist_host.clear(); ctx->clash_over_host.clear();
+    if (n_atoms < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (n_atoms >= 0x80000000LL) return fail(MKAMD_EINVAL, "too many atoms (>= 2^31)");
+    if (n_atoms > 0 && (!coords || !radii || !sel1 || (!self_mode && !sel2))) return fail(MKAMD_EINVAL, "NULL pointer");
+    if ((ex_start == nullptr) != (ex_partner == nullptr)) return fail(MKAMD_EINVAL, "exclusions: both arrays or neither");
+    size_t n_ex = 0;
+    if (ex_start && n_atoms > 0) {                                    // a CSR of ascending rows over n_atoms atoms, partners below n_atoms
+        if (ex_start[0] != 0) return fail(MKAMD_EINVAL, "exclusions: ex_start[0] must be 0");
+        for (int64_t a = 0; a < n_atoms; ++a) {
+            if (ex_start[a + 1] < ex_start[a]) return fail(MKAMD_EINVAL, "exclusions: ex_start must not decrease");
+            for (uint32_t k = ex_start[a]; k < ex_start[a + 1]; ++k) {
+                if (ex_partner[k] >= (uint64_t)n_atoms) return fail(MKAMD_EINVAL, "exclusions: partner index out of range");
+                if (k > ex_start[a] && ex_partner[k] <= ex_partner[k - 1]) return fail(MKAMD_EINVAL, "exclusions: a row must ascend strictly");
+            }
+        }
+        n_ex = ex_start[n_atoms];
+    }
+    void *dc = nullptr, *dr = nullptr, *d1 = nullptr, *d2 = nullptr, *des = nullptr, *dep = nullptr;
+    if (n_atoms > 0) {
+        if ((st = upload(ctx, WS_H_COORDS, coords, (size_t)n_atoms * 12, &dc)) || (st = upload(ctx, WS_H_SIGMAS, radii, (size_t)n_atoms * 4, &dr)) ||
+            (st = upload(ctx, WS_H_OFFSETS, sel1, (size_t)n_atoms * 4, &d1)))
+            return st;
+        if (!self_mode && (st = upload(ctx, WS_H_ORIGINS, sel2, (size_t)n_atoms * 4, &d2))) return st;
+        if (ex_start && ((st = upload(ctx, WS_H_BOX, ex_start, ((size_t)n_atoms + 1) * 4, &des)) || (st = upload(ctx, WS_H_CENTERS, ex_partner, n_ex * 4, &dep))))
+            return st;
+    }
+    mkamd::ClashResult R;
+    if ((st = find_clashes_impl(ctx, (const float*)dc, (const float*)dr, (const uint32_t*)d1, (const uint32_t*)d2, n_atoms, self_mode, (const uint32_t*)des,
+                                (const uint32_t*)dep, overlap, cutoff, max_boxes, R, info))) {
+        (void)hipStreamSynchronize(ctx->stream);                      // (the uploads read the caller's arrays)
+        return st;
+    }
+    if (R.n_pairs) {
+        const size_t k = (size_t)R.n_pairs;
+        std::vector<int> p(2 * k);
+        std::vector<float> d(k), o(k);
+        if ((st = ctx->to_host(p.data(), R.pairs, k * 8)) || (st = ctx->to_host(d.data(), R.dists, k * 4)) || (st = ctx->to_host(o.data(), R.overs, k * 4)))
+            return st;
+        std::vector<size_t> order(k);
+        for (size_t i = 0; i < k; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+            if (o[x] != o[y]) return o[x] > o[y];                     // the largest overlap first
+            if (p[2 * x] != p[2 * y]) return p[2 * x] < p[2 * y];
+            return p[2 * x + 1] < p[2 * y + 1];
+        });
+        ctx->clash_pairs_host.resize(2 * k); ctx->clash_dist_host.resize(k); ctx->clash_over_host.resize(k);
+        for (size_t i = 0; i < k; ++i) {
+            ctx->clash_pairs_host[2 * i] = p[2 * order[i]];
+            ctx->clash_pairs_host[2 * i + 1] = p[2 * order[i] + 1];
+            ctx->clash_dist_host[i] = d[order[i]];
+            ctx->clash_over_host[i] = o[order[i]];
+        }
+        *pairs = ctx->clash_pairs_host.data(); *dist = ctx->clash_dist_host.data(); *overlap_out = ctx->clash_over_host.data();
     } else {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }

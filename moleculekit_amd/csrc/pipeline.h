@@ -58,6 +58,9 @@ enum WsSlot {
     WS_HB_TABLE, WS_HB_MASK, WS_HB_CNT, WS_HB_TOT, WS_HB_BASE, WS_HB_TRIPLES,
     // bond guesser (bond_pipeline.h): status words; its scans' chunk sums; two words per box; the per-atom arrays; the context-owned list
     WS_BD_STAT, WS_BD_CHUNKS, WS_BD_BOXCNT, WS_BD_BOXLOW, WS_BD_ATOMBOX, WS_BD_A, WS_BD_B, WS_BD_START, WS_BD_TMP, WS_BD_ORDER, WS_BD_PAIRS,
+    // steric clashes (clash_pipeline.h; the cell list is the bond guesser's and uses its slots, WS_BD_PAIRS apart): the selection's flags
+    // and numbering; the selected atoms' coordinates and indices; the cell-ordered records; the owners; the three context-owned lists
+    WS_CL_FLAG, WS_CL_POS, WS_CL_SUBCOORDS, WS_CL_SUBATOM, WS_CL_REC, WS_CL_IDX, WS_CL_BITS, WS_CL_BOX, WS_CL_OWNER, WS_CL_PAIRS, WS_CL_DIST, WS_CL_OVER,
     WS_NSLOTS
 };
 
