@@ -487,6 +487,32 @@ int mkamd_find_clashes_host(mkamd_ctx* ctx, const float* coords, const float* ra
  * Both produce the same rows in the same order. */
 int mkamd_ctx_set_clash_plan(mkamd_ctx* ctx, int avoid_mask);
 
+/* ---- proximity selections over frames (moleculekit atomselect_utils.pyx: `within_distance`, behind `within X of ...`) ----
+ *   coords                        _dev: float32 [n_frames][n_atoms][3], frame-major; _host: float32 [n_atoms][3][n_frames], the
+ *                                 reference's layout -- only the rows of the atoms sel1 and sel2 name travel
+ *   sel1 uint32 [n1]              the queries: atom indices < n_atoms in any order, duplicates allowed (the _dev call trusts them)
+ *   sel2 uint32 [n2]              the sources, likewise; may overlap sel1
+ *   cutoff                        float32; within where ((dx dx) + dy dy) + dz dz < cutoff * cutoff, strictly, every float32 operation
+ *                                 rounded on its own.  Zero, NaN and negative cutoffs, and cutoffs whose square overflows or underflows,
+ *                                 behave as that float32 arithmetic says; a NaN anywhere decides "not within"
+ *   gate float32 [n_frames][2][3] per frame (min[3], max[3]), or NULL: no gate.  With it a query is looked at only where on some axis
+ *                                 x >= min - cutoff or x <= max + cutoff in float32 -- the reference's test, which closes with NaNs and
+ *                                 with a negative cutoff
+ *   out uint8 [n_frames][n1]      1 where some source is within of the query, 0 otherwise; every element is written
+ * The _dev call is asynchronous on the context's stream where it takes the all-pairs kernel (always with n_frames > 1).  One frame
+ * with 2 048 sources or more runs over a cell list of the sources, with two round trips; that path is left for the all-pairs kernel, at the same
+ * results, where a box would hold more than 4 096 sources, a source coordinate is not finite, the square of the cutoff is not finite
+ * or the grid is a single box.  mkamd_ctx_last_dist_kernel names the kernel that decided: "mkamd::k_within_pairs",
+ * "mkamd::k_within_cells", or "" where there was nothing to search.
+ * MKAMD_EINVAL: a negative size; 2^31 atoms or more; (_host) an index >= n_atoms. */
+int mkamd_within_distance_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t n_frames, const uint32_t* d_sel1, int64_t n1,
+                              const uint32_t* d_sel2, int64_t n2, float cutoff, const float* d_gate, uint8_t* d_out);
+int mkamd_within_distance_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const uint32_t* sel1, int64_t n1,
+                               const uint32_t* sel2, int64_t n2, float cutoff, const float* gate, uint8_t* out);
+/* The launch plan of the proximity calls (tests, same-box A-B timing).  avoid_mask: 1 not the all-pairs kernel (one frame: the cell list
+ * wherever it can run), 2 not the cell list (default 0: the cell list for one frame from 2 048 sources on).  Both give the same bytes. */
+int mkamd_ctx_set_within_plan(mkamd_ctx* ctx, int avoid_mask);
+
 #ifdef __cplusplus
 }
 #endif

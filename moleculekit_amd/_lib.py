@@ -166,6 +166,10 @@ SIGNATURES = {
     "mkamd_find_clashes_host": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _vp, _vp, _c_dbl, _c_dbl, _c_dbl, ctypes.POINTER(_c_i64),
                                          ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "mkamd_ctx_set_clash_plan": (_c_int, [_vp, _c_int]),
+    # include/mkamd_distance.h, proximity selections
+    "mkamd_within_distance_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_float, _vp, _vp]),
+    "mkamd_within_distance_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_float, _vp, _vp]),
+    "mkamd_ctx_set_within_plan": (_c_int, [_vp, _c_int]),
 }
 
 # operations of mkamd_selftest_arith (csrc/arith_probe.h): name -> (code, arrays read, their dtype, result dtype, results per element)
@@ -459,6 +463,11 @@ class Context:
         a wave per owner.  Both produce the same rows (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_clash_plan(self._h, int(avoid_mask)))
 
+    def set_within_plan(self, avoid_mask: int = 0):
+        """The launch plan of the proximity calls (include/mkamd_distance.h): avoid 1 the all-pairs kernel, 2 the cell list of one
+        frame.  Both produce the same bytes (tests, A-B timing)."""
+        _check(load().mkamd_ctx_set_within_plan(self._h, int(avoid_mask)))
+
     def set_reduction_block(self, block: int = 0):
         """0: choose; 4 / 8: first-group atoms a wave of the closest-atom group reduction keeps in registers; -1: the generic kernel."""
         _check(load().mkamd_ctx_set_reduction_block(self._h, int(block)))
@@ -680,6 +689,21 @@ class Context:
         clash call; 0 when empty), info) -- the rows in the pair kernels' order."""
         return self._find_clashes(load().mkamd_find_clashes_dev, d_coords, d_radii, d_sel1, d_sel2, N, d_ex_start, d_ex_partner, overlap, cutoff,
                                   max_boxes)
+
+    def within_distance_dev(self, d_coords, N, F, d_sel1, n1, d_sel2, n2, cutoff, d_gate, d_out):
+        """coords float32 [F, N, 3], the index lists (uint32), the gate bounds float32 [F, 2, 3] or None and out uint8 [F, n1], all on
+        the device; asynchronous on the context's stream where the all-pairs kernel takes the call."""
+        _check(load().mkamd_within_distance_dev(self._h, _ptr(d_coords), N, F, _ptr(d_sel1), n1, _ptr(d_sel2), n2, float(cutoff), _ptr(d_gate),
+                                                _ptr(d_out)))
+
+    def within_distance_host(self, coords, sel1, sel2, cutoff, gate=None):
+        """float32 [N, 3, F] (the reference's layout), uint32 index arrays, gate float32 [F, 2, 3] or None -> uint8 [F, n1]; only the
+        rows of the atoms either list names travel."""
+        N, _, F = coords.shape
+        out = np.zeros((F, len(sel1)), dtype=np.uint8)
+        _check(load().mkamd_within_distance_host(self._h, _ptr(coords), N, F, _ptr(sel1), len(sel1), _ptr(sel2), len(sel2), float(cutoff),
+                                                 _ptr(gate), _ptr(out)))
+        return out
 
     def guess_bonds_dev(self, d_coords, d_radii, d_is_hydrogen, N, grid_cutoff, max_boxes=4e6, cutoff_incr=1.26):
         """the three arrays on the device -> (address of the device list of 2 n int32 (context-owned until the next bond call; 0 when

@@ -20,6 +20,7 @@
 #include "hbond_pipeline.h"
 #include "bond_pipeline.h"
 #include "clash_pipeline.h"
+#include "within_pipeline.h"
 #include "arith_probe.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
@@ -129,6 +130,7 @@ struct mkamd_ctx {
     std::vector<int> clash_pairs_host;     // results of the last mkamd_find_clashes_host call (owned here)
     std::vector<float> clash_dist_host, clash_over_host;
     int clash_avoid = 0;                   // mkamd_ctx_set_clash_plan
+    int within_avoid = 0;                  // mkamd_ctx_set_within_plan
     std::vector<float> packed_coords;      // the selected atoms' rows of a host distance call (host_pack.h), kept between calls
     std::vector<float> f32_stage;          // host staging of big float64-out results
     struct PendingHostCall { bool active = false; size_t out_bytes = 0; bool mapped_out = false; unsigned seq = 0; void* dout = nullptr; hipEvent_t done = nullptr; };
@@ -2624,6 +2626,62 @@ try {
     }
     *n = R.n_pairs;
     return MKAMD_OK;
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// proximity selections (include/mkamd_distance.h "proximity selections"; within_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_ctx_set_within_plan(mkamd_ctx* ctx, int avoid_mask)
+try {
+    if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
+    if (avoid_mask < 0 || avoid_mask > 2) return fail(MKAMD_EINVAL, "within plan: avoid mask 0, 1 (not the all-pairs kernel) or 2 (not the cell list)");
+    ctx->within_avoid = avoid_mask;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_within_distance_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t n_frames, const uint32_t* d_sel1, int64_t n1,
+                                         const uint32_t* d_sel2, int64_t n2, float cutoff, const float* d_gate, uint8_t* d_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    mkamd::WithinArgs a;
+    a.coords = d_coords; a.n_atoms = n_atoms; a.n_frames = n_frames;
+    a.sel1 = d_sel1; a.n1 = n1; a.sel2 = d_sel2; a.n2 = n2;
+    a.cutoff = cutoff; a.gate = d_gate; a.out = d_out;
+    mkamd::WithinResult R;
+    std::string err;
+    st = mkamd::run_within(*ctx, a, R, err, ctx->within_avoid);
+    return run_status(st, err);
+} MK_API_CATCH
+
+extern "C" int mkamd_within_distance_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const uint32_t* sel1, int64_t n1,
+                                          const uint32_t* sel2, int64_t n2, float cutoff, const float* gate, uint8_t* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    const int64_t N = n_atoms, F = n_frames;
+    if (N < 0 || F < 0 || n1 < 0 || n2 < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (N >= 0x80000000LL) return fail(MKAMD_EINVAL, "too many atoms (>= 2^31)");
+    ctx->note_dist_kernel("");
+    if (F == 0 || n1 == 0) return MKAMD_OK;
+    if (!out || !sel1 || (n2 > 0 && !sel2)) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (n2 == 0) { memset(out, 0, (size_t)F * (size_t)n1); return MKAMD_OK; }
+    if (!coords) return fail(MKAMD_EINVAL, "NULL pointer");
+    if ((st = check_indices(sel1, n1, N, "sel1")) || (st = check_indices(sel2, n2, N, "sel2"))) return st;
+    void *dxyz, *d1, *d2, *dg = nullptr, *dout;
+    HostStage up(ctx, coords, N, F, {{sel1, n1}, {sel2, n2}}, /*always=*/true);      // only the rows of sel1 and sel2 travel
+    if ((st = upload_frame_major(ctx, WS_H_COORDS, WS_WI_XYZ, up.host_rows(), 3 * up.rows(), F, &dxyz))) return st;
+    if ((st = up.list_to(WS_D_SEL1, sel1, n1, &d1))) return st;
+    if ((st = up.list_to(WS_D_SEL2, sel2, n2, &d2))) return st;
+    if ((st = up.sync())) return st;
+    if (gate && (st = upload(ctx, WS_WI_GATE, gate, (size_t)F * 6 * 4, &dg))) return st;
+    if ((st = ctx->ensure(WS_H_OUT, (size_t)F * (size_t)n1, &dout, 0))) return st;
+    if ((st = mkamd_within_distance_dev(ctx, (const float*)dxyz, up.rows(), F, (const uint32_t*)d1, n1, (const uint32_t*)d2, n2, cutoff, (const float*)dg,
+                                        (uint8_t*)dout))) {
+        (void)hipStreamSynchronize(ctx->stream);                      // (the uploads read the caller's arrays)
+        return st;
+    }
+    return download(ctx, out, dout, (size_t)F * (size_t)n1, false);
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------

@@ -61,6 +61,9 @@ enum WsSlot {
     // steric clashes (clash_pipeline.h; the cell list is the bond guesser's and uses its slots, WS_BD_PAIRS apart): the selection's flags
     // and numbering; the selected atoms' coordinates and indices; the cell-ordered records; the owners; the three context-owned lists
     WS_CL_FLAG, WS_CL_POS, WS_CL_SUBCOORDS, WS_CL_SUBATOM, WS_CL_REC, WS_CL_IDX, WS_CL_BITS, WS_CL_BOX, WS_CL_OWNER, WS_CL_PAIRS, WS_CL_DIST, WS_CL_OVER,
+    // proximity selections (within_pipeline.h; the cell list is the bond guesser's and uses its slots): the compacted sources, their
+    // bounding boxes per frame, the cell-ordered source records; the host entry point's frame-major coordinates and gate bounds
+    WS_WI_SRC, WS_WI_BOX, WS_WI_REC, WS_WI_XYZ, WS_WI_GATE,
     WS_NSLOTS
 };
 
