@@ -1845,8 +1845,8 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
     // need two workgroup barriers between them, not four (a barrier of four unevenly loaded waves is ~0.3 us of a 28 us call)
     __shared__ unsigned bucket_cur[TEAM > 1 ? NBUCKET3 + 1 : 1];
     // the hot kernel culls once and keeps the survivors (see SURV_CAP).  The list BORROWS the z array of the entry buffer:
-    // it is written by the cull pass, read by the histogram pass, and moved into registers (eight 16-bit codes per lane)
-    // before the placement pass starts writing entries -- no LDS of its own, so every tier keeps its occupancy
+    // it is written by the cull pass and read by the histogram pass, which decodes every survivor ONCE and keeps it in
+    // registers (eight per lane) for the placement pass -- no LDS of its own, so every tier keeps its occupancy
     constexpr bool SURV_LIST = TEAM == 1 && !DENSE;
     // a team's waves share ONE survivor list: every wave culls its share of the candidate chunks once and appends what
     // survives (tile-relative position, class ids, x-reach) -- the placement pass then walks ~450 survivors split over the
@@ -1864,7 +1864,11 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
     unsigned short* const s_surv = reinterpret_cast<unsigned short*>(sz);
     static_assert(2 * ESTRIDE >= SURV_CAP, "the survivor codes fit the z array");
     constexpr int SURV_REGS = (SURV_CAP + WAVE - 1) / WAVE;
-    unsigned surv_code[SURV_REGS];                          // this lane's codes (survivors lane, lane + 64, ...), for the placement pass
+    // this lane's survivors (lane, lane + 64, ...) as the histogram pass decoded them, for the placement pass: tile-relative
+    // position, the id word the tile sorts by (0 past nsurv) and the x-reach, two bits per survivor in one word
+    float surv_x[SURV_REGS], surv_y[SURV_REGS], surv_z[SURV_REGS];
+    unsigned surv_ids[SURV_REGS], surv_xr = 0u;
+    unsigned surv_code[SURV_REGS];                          // (MK_AB & 4 only: the codes instead, decoded a second time by the placement pass)
 
     const int lane = threadIdx.x & (WAVE - 1);
     const int wv = TEAM > 1 ? (int)(threadIdx.x >> 6) : 0;
@@ -1994,7 +1998,8 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
         //      histogram over the survivors only ----
         unsigned nsurv = 0u;                                  // wave-uniform
         bool use_list = false;
-        // survivor i of the list: its record again (an L2-hot gather), tile-relative; f(valid, ., x, y, z, class ids)
+        // survivor i of the list: its record again (an L2-hot gather), tile-relative; f(register, valid, x, y, z, class ids, pk) --
+        // `register` = i / 64 is a constant of the unrolled loops, so what f keeps per survivor stays in named registers
         auto for_each_survivor = [&](auto from_regs_, auto&& f) {
             constexpr bool FROM_REGS = decltype(from_regs_)::value != 0;
             constexpr int SB = SURV_BATCH;
@@ -2020,9 +2025,20 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
                     const float ex = P[u].x + ((float)(pk & 1023) * tg.fcs + tg.offx);
                     const float ey = P[u].y + ((float)((pk >> 10) & 1023) * tg.fcs + tg.offy);
                     const float ez = P[u].z + ((float)((pk >> 20) & 1023) * tg.fcs + tg.offz);
-                    f(ok[u], 0u, ex, ey, ez, ids[u], pk);
+                    f(cb + u, ok[u], ex, ey, ez, ids[u], pk);
                 }
             }
+        };
+        // the histogram pass over the list is the ONLY place where a survivor's code becomes data: what it counts it keeps
+        // (ids is 0 in a lane past nsurv, and sort_ids leaves 0 alone)
+        auto count_and_keep = [&](int j, bool surv, float ex, float ey, float ez, unsigned ids, int pk) {
+            const int xr = x_reach(ex, ey, ez, pk);
+            ids = sort_ids(surv ? ids : 0u);
+            surv_x[j] = ex; surv_y[j] = ey; surv_z[j] = ez; surv_ids[j] = ids;
+            surv_xr |= (unsigned)xr << (2 * j);
+            for_each_present_channel(ids, [&](int c, unsigned id) {
+                (void)mk_lds_add(&bucket[(c * NSLOT + (int)id - 1) * NXR + xr], 1u);
+            });
         };
         if constexpr (SURV_LIST) {
             // (worth it when most candidates are rejected, i.e. when there are many: a sparse tile's few chunks go the old way)
@@ -2037,14 +2053,28 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
                 use_list = nsurv <= (unsigned)SURV_CAP;
                 mk_block_sync();                              // the list is read by other lanes than wrote it
                 if (use_list) {
-                    if (!(MK_DIAG & 32)) for_each_survivor(IntC<0>{}, count_entry);
+                    // the last reader of the codes in the z array: the mk_block_sync behind the traversals (below, in front of
+                    // "bucket starts") and the two in place() lie between these reads and the first entry the placement stores
+                    if (MK_AB & 4) {                          // the parent's histogram pass: counts, keeps nothing
+                        for_each_survivor(IntC<0>{}, [&](int, bool surv, float ex, float ey, float ez, unsigned ids, int pk) {
+                            count_entry(surv, 0u, ex, ey, ez, ids, pk);
+                        });
+                    } else if (!(MK_DIAG & 32)) {
+                        for_each_survivor(IntC<0>{}, count_and_keep);
+                    } else {
 #pragma unroll
-                    for (int cb = 0; cb < SURV_REGS; ++cb) {              // the codes leave the z array before entries go in
-                        const unsigned i = (unsigned)(cb * WAVE + lane);
-                        surv_code[cb] = i < nsurv ? (unsigned)s_surv[i] : 0u;
+                        for (int j = 0; j < SURV_REGS; ++j) { surv_x[j] = surv_y[j] = surv_z[j] = 0.f; surv_ids[j] = 0u; }
+                    }
+                    if (MK_AB & 4) {
+#pragma unroll
+                        for (int cb = 0; cb < SURV_REGS; ++cb) {          // the codes leave the z array before entries go in
+                            const unsigned i = (unsigned)(cb * WAVE + lane);
+                            surv_code[cb] = i < nsurv ? (unsigned)s_surv[i] : 0u;
+                        }
                     }
                 }
             }
+            MK_SURV_PROBE(lt, gq, runs.N, nsurv, use_list, surv_xr);
         }
         if (MK_DIAG & 16) {
         } else if (use_list) {
@@ -2266,7 +2296,19 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
             };
             if (MK_DIAG & 64) {
             } else if (use_list) {
-                for_each_survivor(IntC<1>{}, place_entry);
+                if (MK_AB & 4) {                                                 // the A-B of the kept survivors: decode them again
+                    for_each_survivor(IntC<1>{}, [&](int, bool surv, float ex, float ey, float ez, unsigned ids, int pk) {
+                        place_entry(surv, 0u, ex, ey, ez, ids, pk);
+                    });
+                } else {
+#pragma unroll
+                    for (int j = 0; j < SURV_REGS; ++j) {
+                        if ((unsigned)(j * WAVE) >= nsurv) break;                // wave-uniform
+                        // (MK_DIAG & 256: register 0 reads register 1's x-reach, the mutation tests/test_emu_survivor_regs.py must catch)
+                        const int sh = ((MK_DIAG & 256) && j == 0) ? 2 : 2 * j;
+                        place_at(true, surv_x[j], surv_y[j], surv_z[j], surv_ids[j], (int)((surv_xr >> sh) & 3u));
+                    }
+                }
             } else if (use_sv) {
                 for (unsigned i = (unsigned)(wv * WAVE + lane); i < nsv; i += (unsigned)(TEAM * WAVE))     // per-lane trip count: no collectives inside
                     place_at(true, sv_x[i], sv_y[i], sv_z[i], sv_ids[i], (int)sv_xr[i]);

@@ -13,15 +13,23 @@
 //                      traversal (profiles/r4_tile_time_map.txt, profiles/r5_tile_instruction_map.txt),
 //                      128 the cover fold of the class flush while channel 7 still leaves the covered atoms out (the mutation
 //                      tests/test_emu_cover_fold.py must catch)
+//                      256 the placement over the kept survivors reads register 1's x-reach for register 0 (the mutation
+//                      tests/test_emu_survivor_regs.py must catch)
 //   MK_PHASE_TIMERS    cycle counters around the phases of a tile wave (tools/phase_timers.py); with MK_BIN_TIMERS the
 //                      sections of k_bin_direct instead (tools/bin_timers.py).  Values stay right, timing does not.
+//   MK_AB=<bits>       two CORRECT code paths on one source, for counter differences (values stay right): 1 the cover fold per
+//                      group instead of once per channel, 2 the per-chunk search of the runs instead of the cursor, 4 the
+//                      histogram pass keeps nothing and the placement pass decodes the survivor list a second time (codes
+//                      kept in registers, records gathered again), as before round 10
+//   MK_SURV_PROBE      host emulation only: voxelize_tile reports a tile's candidates, survivors, path and packed x-reach
+//                      word to mk_surv_probe(), which the including translation unit defines (tests/emu/emu_survivor_regs.cpp).
 // Experiments that were measured and ruled out (single-entry groups evaluated directly, the rolled channel loop, the
 // trip-cut timing build, the kernel without its general path, LDS padding, the two-traversal kernel of round 1) are in
 // docs/EXPERIMENTS_r3.md / _r4.md and in the history of kernels.h, not in the product source.
 #pragma once
 
-#if (defined(MK_DIAG) || defined(MK_PHASE_TIMERS) || defined(MK_BIN_TIMERS)) && !defined(MKAMD_DIAGNOSTICS_BUILD)
-#error "MK_DIAG / MK_PHASE_TIMERS / MK_BIN_TIMERS change the product kernels: diagnostics builds must pass -DMKAMD_DIAGNOSTICS_BUILD (tools/build_variant.sh)"
+#if (defined(MK_DIAG) || defined(MK_PHASE_TIMERS) || defined(MK_BIN_TIMERS) || defined(MK_SURV_PROBE)) && !defined(MKAMD_DIAGNOSTICS_BUILD)
+#error "MK_DIAG / MK_PHASE_TIMERS / MK_BIN_TIMERS / MK_SURV_PROBE change the product kernels: diagnostics builds must pass -DMKAMD_DIAGNOSTICS_BUILD (tools/build_variant.sh)"
 #endif
 
 #ifndef MK_DIAG
@@ -67,6 +75,13 @@ namespace mkamd { __device__ unsigned long long g_phase_cycles[8]; }
 #else
 #define MK_BIN_MARK(i) do {} while (0)
 #define MK_BIN_BEGIN() do {} while (0)
+#endif
+
+#ifdef MK_SURV_PROBE
+#undef MK_SURV_PROBE
+#define MK_SURV_PROBE(lt, gq, n, nsurv, use_list, xr_word) mk_surv_probe(lt, gq, (int)threadIdx.x, n, nsurv, use_list, xr_word)
+#else
+#define MK_SURV_PROBE(lt, gq, n, nsurv, use_list, xr_word) do {} while (0)
 #endif
 
 #ifdef MKAMD_DIAGNOSTICS_BUILD
