@@ -513,6 +513,28 @@ int mkamd_within_distance_host(mkamd_ctx* ctx, const float* coords, int64_t n_at
  * wherever it can run), 2 not the cell list (default 0: the cell list for one frame from 2 048 sources on).  Both give the same bytes. */
 int mkamd_ctx_set_within_plan(mkamd_ctx* ctx, int avoid_mask);
 
+/* ---- secondary structure: Kabsch and Sander's DSSP of every frame (moleculekit projections/metricsecondarystructure.py, which
+ * hands the frames to an external implementation one at a time).  The rules are stated in DESIGN.md section 19: backbone N-H...O=C
+ * energies in float32, every operation rounded once, between residues whose CA atoms are closer than 9 A; the two best acceptors of
+ * every donor; n-turns, helices, bends, bridges and ladders with bulge merging.  No box is used. ----
+ *   coords float32 [n_atoms][3][n_frames]   the reference's layout, in A; _host: only the rows of the 4 R backbone atoms travel
+ *   ca uint32 [R], nco uint32 [R][3]        the CA atom of every residue, and its N, C, O (the _dev call trusts the indices)
+ *   proline int32 [R]                       not 0: the residue donates no hydrogen bond
+ *   chain int32 [R]                         equal in neighbouring residues: the same chain
+ *   simplified                              0: out holds H 3, B 4, E 5, G 6, I 7, T 8, S 9, ' ' 10; else helix 2, strand 1, coil 0
+ *   out uint8 [n_frames][R]                 every element is written
+ * The _dev call is asynchronous on the context's stream.  The same bytes on every run and under either launch plan;
+ * mkamd_ctx_last_dist_kernel names the energy kernel: "mkamd::k_dssp_energy_frames" or "mkamd::k_dssp_energy_atoms".
+ * MKAMD_EINVAL: a negative size; 2^30 frames or more; more than 2^18 residues; (_host) an index >= n_atoms. */
+int mkamd_dssp_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t n_frames, const uint32_t* d_ca, const uint32_t* d_nco,
+                   const int32_t* d_proline, const int32_t* d_chain, int64_t R, int simplified, uint8_t* d_out);
+int mkamd_dssp_host(mkamd_ctx* ctx, const float* coords, int64_t n_atoms, int64_t n_frames, const uint32_t* ca, const uint32_t* nco,
+                    const int32_t* proline, const int32_t* chain, int64_t R, int simplified, uint8_t* out);
+/* The launch plan of the secondary-structure calls (tests, same-box A-B timing).  avoid_mask: 1 not the energy kernel with lanes along
+ * frames, 2 not the one with lanes along acceptors (default 0: lanes along acceptors while n_frames * R < 32 768, where the two were measured to cross), 4 chunks of 64 frames whatever
+ * the workspace allows.  Every plan gives the same bytes. */
+int mkamd_ctx_set_dssp_plan(mkamd_ctx* ctx, int avoid_mask);
+
 #ifdef __cplusplus
 }
 #endif

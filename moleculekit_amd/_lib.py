@@ -170,6 +170,10 @@ SIGNATURES = {
     "mkamd_within_distance_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_float, _vp, _vp]),
     "mkamd_within_distance_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.c_float, _vp, _vp]),
     "mkamd_ctx_set_within_plan": (_c_int, [_vp, _c_int]),
+    # include/mkamd_distance.h, secondary structure
+    "mkamd_dssp_dev": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _c_int, _vp]),
+    "mkamd_dssp_host": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_i64, _c_int, _vp]),
+    "mkamd_ctx_set_dssp_plan": (_c_int, [_vp, _c_int]),
 }
 
 # operations of mkamd_selftest_arith (csrc/arith_probe.h): name -> (code, arrays read, their dtype, result dtype, results per element)
@@ -467,6 +471,12 @@ class Context:
         """The launch plan of the proximity calls (include/mkamd_distance.h): avoid 1 the all-pairs kernel, 2 the cell list of one
         frame.  Both produce the same bytes (tests, A-B timing)."""
         _check(load().mkamd_ctx_set_within_plan(self._h, int(avoid_mask)))
+
+    def set_dssp_plan(self, avoid_mask: int = 0):
+        """The launch plan of the secondary-structure calls (include/mkamd_distance.h): avoid 1 the energy kernel with lanes along
+        frames, 2 the one with lanes along acceptors (default: acceptors while frames x residues < 32 768); + 4: chunks of 64 frames.  Every plan produces the same bytes (tests, A-B
+        timing); ``last_dist_kernel`` names the energy kernel that ran."""
+        _check(load().mkamd_ctx_set_dssp_plan(self._h, int(avoid_mask)))
 
     def set_reduction_block(self, block: int = 0):
         """0: choose; 4 / 8: first-group atoms a wave of the closest-atom group reduction keeps in registers; -1: the generic kernel."""

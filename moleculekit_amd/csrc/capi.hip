@@ -21,6 +21,7 @@
 #include "bond_pipeline.h"
 #include "clash_pipeline.h"
 #include "within_pipeline.h"
+#include "dssp_pipeline.h"
 #include "arith_probe.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
@@ -131,6 +132,7 @@ struct mkamd_ctx {
     std::vector<float> clash_dist_host, clash_over_host;
     int clash_avoid = 0;                   // mkamd_ctx_set_clash_plan
     int within_avoid = 0;                  // mkamd_ctx_set_within_plan
+    int dssp_avoid = 0;                    // mkamd_ctx_set_dssp_plan
     std::vector<float> packed_coords;      // the selected atoms' rows of a host distance call (host_pack.h), kept between calls
     std::vector<float> f32_stage;          // host staging of big float64-out results
     struct PendingHostCall { bool active = false; size_t out_bytes = 0; bool mapped_out = false; unsigned seq = 0; void* dout = nullptr; hipEvent_t done = nullptr; };
@@ -2682,6 +2684,59 @@ try {
         return st;
     }
     return download(ctx, out, dout, (size_t)F * (size_t)n1, false);
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// secondary structure (include/mkamd_distance.h "secondary structure"; dssp_pipeline.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_ctx_set_dssp_plan(mkamd_ctx* ctx, int avoid_mask)
+try {
+    if (!ctx) return fail(MKAMD_EINVAL, "ctx is NULL");
+    if (avoid_mask < 0 || avoid_mask > 7 || (avoid_mask & 3) == 3)
+        return fail(MKAMD_EINVAL, "dssp plan: avoid mask 1 (not the frame-lane energy kernel) or 2 (not the acceptor-lane one), + 4 (chunks of 64 frames)");
+    ctx->dssp_avoid = avoid_mask;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_dssp_dev(mkamd_ctx* ctx, const float* d_coords, int64_t n_atoms, int64_t F, const uint32_t* d_ca, const uint32_t* d_nco,
+                              const int32_t* d_proline, const int32_t* d_chain, int64_t R, int simplified, uint8_t* d_out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (n_atoms < 0 || F < 0 || R < 0) return fail(MKAMD_EINVAL, "negative size");
+    std::string err;
+    st = mkamd::run_dssp(*ctx, d_coords, F, d_ca, d_nco, d_proline, d_chain, R, simplified, d_out, err, ctx->dssp_avoid,
+                         [](const mkamd::DsspWs&, long long, long long) { return 0; });
+    return run_status(st, err);
+} MK_API_CATCH
+
+extern "C" int mkamd_dssp_host(mkamd_ctx* ctx, const float* coords, int64_t N, int64_t F, const uint32_t* ca, const uint32_t* nco,
+                               const int32_t* proline, const int32_t* chain, int64_t R, int simplified, uint8_t* out)
+try {
+    int st = check_ctx(ctx);
+    if (st) return st;
+    if (N < 0 || F < 0 || R < 0) return fail(MKAMD_EINVAL, "negative size");
+    if (F > 0x3fffffffLL) return fail(MKAMD_EINVAL, "too many frames (>= 2^30)");
+    if (R > mkamd::DSSP_MAX_RESIDUES) return fail(MKAMD_EINVAL, "too many residues (> 2^18)");
+    if (F == 0 || R == 0) return MKAMD_OK;
+    if (!coords || !ca || !nco || !proline || !chain || !out) return fail(MKAMD_EINVAL, "NULL pointer");
+    if ((st = check_indices(ca, R, N, "ca: atom")) || (st = check_indices(nco, 3 * R, N, "nco: atom"))) return st;
+    void *dc, *dca, *dnco, *dpro, *dchain, *dout;
+    HostStage up(ctx, coords, N, F, {{ca, R}, {nco, 3 * R}});          // only the backbone atoms' rows travel
+    if ((st = up.coords_to(WS_H_COORDS, &dc))) return st;
+    if ((st = up.list_to(WS_D_SEL1, ca, R, &dca))) return st;
+    if ((st = up.list_to(WS_SS_NCO, nco, 3 * R, &dnco))) return st;
+    if ((st = up.sync())) return st;
+    if ((st = upload(ctx, WS_SS_PROLINE, proline, (size_t)R * 4, &dpro))) return st;
+    if ((st = upload(ctx, WS_D_CHAINS, chain, (size_t)R * 4, &dchain))) return st;
+    if ((st = ctx->ensure(WS_H_OUT, (size_t)F * (size_t)R, &dout, 0))) return st;
+    st = mkamd_dssp_dev(ctx, (const float*)dc, up.rows(), F, (const uint32_t*)dca, (const uint32_t*)dnco, (const int32_t*)dpro,
+                        (const int32_t*)dchain, R, simplified, (uint8_t*)dout);
+    if (st) {
+        (void)hipStreamSynchronize(ctx->stream);                      // (the uploads read the caller's arrays)
+        return st;
+    }
+    return download(ctx, out, dout, (size_t)F * (size_t)R, false);
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------

@@ -64,6 +64,8 @@ enum WsSlot {
     // proximity selections (within_pipeline.h; the cell list is the bond guesser's and uses its slots): the compacted sources, their
     // bounding boxes per frame, the cell-ordered source records; the host entry point's frame-major coordinates and gate bounds
     WS_WI_SRC, WS_WI_BOX, WS_WI_REC, WS_WI_XYZ, WS_WI_GATE,
+    // secondary structure (dssp_pipeline.h): the chain runs, the chunk's arrays; the host entry point's per-residue arrays
+    WS_SS_SEG, WS_SS_WORK, WS_SS_NCO, WS_SS_PROLINE,
     WS_NSLOTS
 };
 
