@@ -65,6 +65,69 @@ constexpr unsigned CLS_EMPTY = 0xffffffffu;   // empty slot of the class table (
 constexpr int CLS_OVERFLOW = NCLS;   // word NCLS of the table buffer: CLS_EMPTY, or 0 once > NCLS classes were seen
 constexpr int CLS_TABLE_WORDS = NCLS + 1;
 
+// The cutoff of a class flush as a MASKED minimum:  acc = (d2 < R2) ? min_u32(acc, bits(val)) : acc.
+// An accumulator starts at the bits of +inf and only ever decreases, so leaving it alone out of range gives the bits of
+// `min_u32(acc, d2 < R2 ? val : +inf)` -- for NaN too: `NaN < R2` is false in both forms -- and costs a compare and a minimum
+// where that form costs a compare, a select and a minimum.  R2 is wave-uniform (GridDesc::R2).
+// Device form: ONE asm statement.  v_cmpx_gt_f32 leaves in EXEC the lanes with R2 > d2 (gfx950 is a GFX9-family target: the
+// e32 form writes VCC too, hence the clobber), the minimum runs in those lanes, and EXEC is back at its saved value before
+// the statement ends -- the compiler never sees it changed.  The trailing s_nop 2 puts five wait states between the VALU
+// write of EXEC and whatever the compiler schedules next (a v_readlane / v_readfirstlane needs four, a DPP operation five;
+// its hazard recogniser does not look into the string).  Scalar instructions all three: no VALU issue slot.
+// Host emulation (tests/emu): the plain C++ form; -DMK_DIAG=512 makes it ignore the cutoff (mk_diagnostics.h).
+MK_DEV void mk_min_bits_where(unsigned& acc, float val, float d2, float R2)
+{
+#if defined(MK_DEVICE_API_PROVIDED) || (MK_DIAG & 512)
+    if ((MK_DIAG & 512) || d2 < R2) acc = mk_min_bits(acc, val);
+#else
+    unsigned long long saved_exec;
+    asm("s_mov_b64 %1, exec\n\t"
+        "v_cmpx_gt_f32_e32 vcc, %4, %3\n\t"
+        "v_min_u32_e32 %0, %2, %0\n\t"
+        "s_mov_b64 exec, %1\n\t"
+        "s_nop 2"
+        : "+v"(acc), "=&s"(saved_exec)
+        : "v"(val), "v"(d2), "s"(R2)
+        : "vcc");
+#endif
+}
+
+// The flush of N planes of one class: acc[k] = (d2[k] < R2) ? min_u32(acc[k], bits(|d2[k]| * w)) : acc[k].  The device form is one
+// asm statement per four planes (two, one: a team's wave owns K / TEAM planes): EXEC is saved ONCE, every plane is multiply, v_cmpx,
+// minimum and a scalar move that puts EXEC back (v_cmpx looks at the lanes EXEC still holds), and ONE s_nop 2 ends the statement.
+// Statement by statement through mk_min_bits_where the same flush issued sixteen scalar moves and eight s_nop 2 per class, and the
+// wave waited on them: 6 782 VALU per tile against the parent's 7 221, and no faster (docs/EXPERIMENTS_r11.md section 3).
+#define MK_MBW_PLANE(a, d) "v_mul_f32_e64 %[t], |%[" d "]|, %[w]\n\tv_cmpx_gt_f32_e32 vcc, %[r2], %[" d "]\n\t" \
+                           "v_min_u32_e32 %[" a "], %[t], %[" a "]\n\ts_mov_b64 exec, %[sx]\n\t"
+template <int N>
+MK_DEV void mk_flush_planes(unsigned (&acc)[N], const float (&d2)[N], float w, float R2)
+{
+#if defined(MK_DEVICE_API_PROVIDED) || (MK_DIAG & 512)
+#pragma unroll
+    for (int k = 0; k < N; ++k) mk_min_bits_where(acc[k], mk_abs(d2[k]) * w, d2[k], R2);
+#else
+    static_assert(N == 1 || N == 2 || N % 4 == 0, "planes per wave: 1, 2 or a multiple of four");
+    unsigned long long sx;
+    float t;
+    if constexpr (N == 1) {
+        asm("s_mov_b64 %[sx], exec\n\t" MK_MBW_PLANE("a0", "d0") "s_nop 2"
+            : [a0] "+v"(acc[0]), [sx] "=&s"(sx), [t] "=&v"(t)
+            : [d0] "v"(d2[0]), [w] "s"(w), [r2] "s"(R2) : "vcc");
+    } else if constexpr (N == 2) {
+        asm("s_mov_b64 %[sx], exec\n\t" MK_MBW_PLANE("a0", "d0") MK_MBW_PLANE("a1", "d1") "s_nop 2"
+            : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [sx] "=&s"(sx), [t] "=&v"(t)
+            : [d0] "v"(d2[0]), [d1] "v"(d2[1]), [w] "s"(w), [r2] "s"(R2) : "vcc");
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k += 4)
+            asm("s_mov_b64 %[sx], exec\n\t" MK_MBW_PLANE("a0", "d0") MK_MBW_PLANE("a1", "d1") MK_MBW_PLANE("a2", "d2") MK_MBW_PLANE("a3", "d3") "s_nop 2"
+                : [a0] "+v"(acc[k]), [a1] "+v"(acc[k + 1]), [a2] "+v"(acc[k + 2]), [a3] "+v"(acc[k + 3]), [sx] "=&s"(sx), [t] "=&v"(t)
+                : [d0] "v"(d2[k]), [d1] "v"(d2[k + 1]), [d2] "v"(d2[k + 2]), [d3] "v"(d2[k + 3]), [w] "s"(w), [r2] "s"(R2) : "vcc");
+    }
+#endif
+}
+#undef MK_MBW_PLANE
+
 // Everything the kernels need to know about the batch of lattice grids (passed by value).
 struct GridDesc {
     int nx, ny, nz;             // voxels per axis (identical for every item of the batch)
@@ -1974,6 +2037,13 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
         for (int i = 0; i < NBUCKET3 / WAVE; ++i) bucket[lane + i * WAVE] = 0u;
         if (TEAM > 1 && threadIdx.x == 0) s_nsv = 0u;
         mk_block_sync();
+        // "this item alone has too many classes" (a per-item table: a fresh line per item) is decided HERE, in front of the
+        // traversals, which such a tile then skips; the general path is entered behind them as before.  The candidate runs,
+        // which the first traversal waits for, were loaded after the table, so the word is there by then.  (Round 11: decided
+        // behind the traversals, the edge into the general path carried the 64 accumulators -- holding nothing -- across the
+        // histogram pass and its kept survivors; with an asm statement in the class flush the register allocator no longer
+        // got round that: docs/EXPERIMENTS_r11.md section 2.)
+        const bool item_general = !DENSE && g.cls_per_item && mk_readlane(table_word, CLS_OVERFLOW) != CLS_EMPTY;   // wave-uniform
         auto count_entry = [&](bool surv, unsigned, float ex, float ey, float ez, unsigned ids, int pk) {
             const int xr = x_reach(ex, ey, ez, pk);
             ids = sort_ids(ids);
@@ -2042,7 +2112,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
         };
         if constexpr (SURV_LIST) {
             // (worth it when most candidates are rejected, i.e. when there are many: a sparse tile's few chunks go the old way)
-            if (!(MK_DIAG & 16) && runs.codable && runs.N > 4u * WAVE) {
+            if (!(MK_DIAG & 16) && !item_general && runs.codable && runs.N > 4u * WAVE) {
                 auto keep_survivor = [&](bool surv, unsigned code, float, float, float, unsigned, int) {
                     const unsigned long long m = mk_ballot(surv);
                     const unsigned pos = nsurv + (unsigned)mk_rank_in_mask(m);
@@ -2077,7 +2147,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
             MK_SURV_PROBE(lt, gq, runs.N, nsurv, use_list, surv_xr);
         }
         if (MK_DIAG & 16) {
-        } else if (use_list) {
+        } else if (use_list || item_general) {
         } else if (TEAM > 1) {
             for_each_candidate<K, true, TRAV_BATCH>(g, tg, runs, rec_pos, clsp, count_and_list, (unsigned)wv, (unsigned)TEAM);
         } else {
@@ -2086,7 +2156,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
         mk_block_sync();
         const unsigned nsv = TEAM > 1 ? mk_uniform(s_nsv) : 0u;             // the same in every wave of the team
         const bool use_sv = TEAM > 1 && nsv <= (unsigned)SV_CAP;
-        if (!DENSE && g.cls_per_item && mk_readlane(table_word, CLS_OVERFLOW) != CLS_EMPTY) {
+        if (item_general) {
             general = true;                      // this item alone has too many classes (its records carry w, not ids)
         } else {
         MK_PHASE_MARK(1);                                   // traversal 1 (histogram)
@@ -2238,12 +2308,27 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
                     run_exact(bg.z, bg.w);
                 }
                 // class flush: cutoff on the class minimum (occupancy_utils.pyx:53), then scale by w
-                if (!(MK_DIAG & 2))
+                // (round 11) `fast` is the same for every lane and plane: ONE scalar branch picks the body, no select per plane;
+                // the cutoff is a masked minimum (mk_min_bits_where: acc only ever decreases from +inf, so "out of range"
+                // is "leave acc alone").  Per plane: add, mul, cmpx, min in a fast class, mul, cmpx, min in an exact one.
+                // The fold per group reads the flushed value back from m[k], and MK_AB & 8 is the A-B of this: both keep
+                // the flush as it was (select per plane, compare, +inf select, unconditional minimum).
+                if (!(MK_DIAG & 2)) {
+                    if ((MK_AB & (1 | 8)) != 0) {
 #pragma unroll
-                for (int k = 0; k < KL; ++k) {
-                    const float d2 = fast ? m[k] + pl_x(k) * pl_x(k) : m[k];         // (plane_d2: g_k + c_k^2)
-                    m[k] = d2 < R2 ? mk_abs(d2) * wcls : INF;
-                    acc[k] = mk_min_bits(acc[k], m[k]);
+                        for (int k = 0; k < KL; ++k) {
+                            const float d2 = fast ? m[k] + pl_x(k) * pl_x(k) : m[k];         // (plane_d2: g_k + c_k^2)
+                            m[k] = d2 < R2 ? mk_abs(d2) * wcls : INF;
+                            acc[k] = mk_min_bits(acc[k], m[k]);
+                        }
+                    } else {
+                        if (fast) {                                       // wave-uniform
+                            mk_stay_in_branch();
+#pragma unroll
+                            for (int k = 0; k < KL; ++k) { m[k] += pl_x(k) * pl_x(k); mk_keep(m[k]); }          // (plane_d2: g_k + c_k^2)
+                        }
+                        mk_flush_planes(acc, m, wcls, R2);
+                    }
                 }
                 // cover fold: channel 7 left these atoms out of its own lists (a team's wave folds its own partial flush)
                 if constexpr (!DENSE) {
@@ -2369,7 +2454,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
                                 entry_d2<K>(e.x, mk_fma(dy, dy, dz * dz), e.w, d2);
 #pragma unroll
                                 for (int k = 0; k < K; ++k)
-                                    m[k] = mk_min_bits(m[k], d2[k] < R2 ? mk_abs(d2[k]) * e.w : INF);   // occupancy_utils.pyx:53
+                                    mk_min_bits_where(m[k], mk_abs(d2[k]) * e.w, d2[k], R2);   // occupancy_utils.pyx:53
                             }
                             mk_block_sync();                                 // ebuf is rewritten next
                         });
@@ -2418,7 +2503,7 @@ MK_DEV void voxelize_tile(const GridDesc& g, const unsigned lt, const int gq, co
                     entry_d2<K>(e.x, mk_fma(dy, dy, dz * dz), e.w, d2);                  // same fma tree as the sorted path
 #pragma unroll
                     for (int k = 0; k < KL; ++k)
-                        q[c][k] = mk_min_bits(q[c][k], d2[k] < R2 ? mk_abs(d2[k]) * e.w : INF);   // occupancy_utils.pyx:53
+                        mk_min_bits_where(q[c][k], mk_abs(d2[k]) * e.w, d2[k], R2);   // occupancy_utils.pyx:53
                 }
                 mk_block_sync();                                     // ebuf is rewritten next
             }
@@ -2653,11 +2738,13 @@ MK_DEV void voxelize_item_tile(const GridDesc& g, const int b, const int t, cons
                 }
             }
             // class flush: cutoff on the class minimum (occupancy_utils.pyx:53), then scale by w
+            // (round 11, as voxelize_tile's process_classes: one scalar branch on `fast`, the cutoff as a masked minimum)
+            if (fast) {                                                   // wave-uniform
+                mk_stay_in_branch();
 #pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const float d2 = fast ? m[k] + plane_x<K>(k) * plane_x<K>(k) : m[k];
-                q[c][k] = mk_min_bits(q[c][k], d2 < R2 ? mk_abs(d2) * wcls : INF);
+                for (int k = 0; k < K; ++k) { m[k] += plane_x<K>(k) * plane_x<K>(k); mk_keep(m[k]); }      // (plane_d2: g_k + c_k^2)
             }
+            mk_flush_planes(q[c], m, wcls, R2);
         }
     }
     // ---- epilogue: q -> occupancy in place (a channel without an entry in reach is all zeros: no rcp / exp for it --
@@ -2802,7 +2889,7 @@ MK_DEV void voxelize_item_tile_unsorted(const GridDesc& g, const int b, const in
                 entry_d2<K>(e.x, mk_fma(dy, dy, dz * dz), e.w, d2);      // same fma tree as the sorted path
 #pragma unroll
                 for (int k = 0; k < K; ++k)
-                    q[c][k] = mk_min_bits(q[c][k], d2[k] < R2 ? mk_abs(d2[k]) * e.w : INF);   // occupancy_utils.pyx:53
+                    mk_min_bits_where(q[c][k], mk_abs(d2[k]) * e.w, d2[k], R2);   // occupancy_utils.pyx:53
             }
             mk_wave_sync();                                              // ebuf is rewritten next
         }

@@ -15,12 +15,15 @@
 //                      tests/test_emu_cover_fold.py must catch)
 //                      256 the placement over the kept survivors reads register 1's x-reach for register 0 (the mutation
 //                      tests/test_emu_survivor_regs.py must catch)
-//   MK_PHASE_TIMERS    cycle counters around the phases of a tile wave (tools/phase_timers.py); with MK_BIN_TIMERS the
+//                      512 mk_min_bits_where, the masked minimum of the class flush, takes its plain C++ form (on the device
+//                      too) and ignores the cutoff (the mutation tests/test_emu_class_flush.py must catch)
+//   MK_PHASE_TIMERS   cycle counters around the phases of a tile wave (tools/phase_timers.py); with MK_BIN_TIMERS the
 //                      sections of k_bin_direct instead (tools/bin_timers.py).  Values stay right, timing does not.
 //   MK_AB=<bits>       two CORRECT code paths on one source, for counter differences (values stay right): 1 the cover fold per
 //                      group instead of once per channel, 2 the per-chunk search of the runs instead of the cursor, 4 the
 //                      histogram pass keeps nothing and the placement pass decodes the survivor list a second time (codes
-//                      kept in registers, records gathered again), as before round 10
+//                      kept in registers, records gathered again), as before round 10, 8 the class flush as before round 11
+//                      (a select on `fast` per plane, compare, +inf select, unconditional minimum: six VALU per plane)
 //   MK_SURV_PROBE      host emulation only: voxelize_tile reports a tile's candidates, survivors, path and packed x-reach
 //                      word to mk_surv_probe(), which the including translation unit defines (tests/emu/emu_survivor_regs.cpp).
 // Experiments that were measured and ruled out (single-entry groups evaluated directly, the rolled channel loop, the
