@@ -63,6 +63,29 @@ struct mkamd_ctx;
 int mkamd_xtc_decode_dev(struct mkamd_ctx* ctx, void* hip_stream, const void* d_bytes, const void* d_desc, int64_t n_frames,
                          int64_t n_atoms, float scale, float* d_xyz, int32_t* d_status, void* d_work, uint64_t work_bytes);
 
+/* Compression ON THE DEVICE (csrc/xtc_encode.h): the file image of frames that are resident on the GPU, byte for byte what the
+ * reference's writer makes of them (xtc_src.cpp: xtc_write :410-469; xdrfile.cpp: xdrfile_compress_coord_float :985-1279 -- runs of
+ * small atoms, the water swap, the adaptive small-number index).  A thread per atom quantises, a lane per frame walks the integers
+ * and records where every group starts, a thread per group packs its bits.
+ *   mkamd_xtc_encode_work_bytes   size of the device work buffer an encode of n_frames x n_atoms needs (~24 bytes per atom)
+ *   mkamd_xtc_encode_bound        upper bound of the image in bytes (13 bytes per atom and 92 per frame, rounded up to words)
+ *   mkamd_xtc_encode_dev          d_xyz f32 [n_frames, n_atoms, 3] (frame-major), times `in_scale` (1 = nm input, the float32 0.1 =
+ *                          Angstrom) with one float32 rounding, as the host path of the reference does before it writes;
+ *                          d_precision f32 [n_frames] (<= 0 is written as 1000), d_box f32 [n_frames, 3, 3] (box vectors, nm),
+ *                          d_time f32 [n_frames] (ps), d_step i32 [n_frames].  Out: d_image (4-byte aligned, image_capacity >=
+ *                          mkamd_xtc_encode_bound bytes; the records one after the other, only bytes below d_offsets[n_frames] are
+ *                          written), d_offsets u64 [n_frames + 1] (a refused frame takes no bytes), d_status i32 [n_frames]: 0 ok,
+ *                          2 outside what the device path takes and nothing of that frame written -- a coordinate that is not
+ *                          finite or leaves the int range at this precision, a range of >= INT_MAX - 2 quanta, a full triple of more
+ *                          than 64 bits, a header small-number index + 8 > 64 (the rule of the device decoder; the reference reads
+ *                          past its own table there), >= 2^21 atoms.  d_work: 8-byte aligned, only used during the call's
+ *                          kernels.  Both sizes are checked before any launch.  Asynchronous on `hip_stream`. */
+uint64_t mkamd_xtc_encode_work_bytes(int64_t n_frames, int64_t n_atoms);
+uint64_t mkamd_xtc_encode_bound(int64_t n_frames, int64_t n_atoms);
+int mkamd_xtc_encode_dev(struct mkamd_ctx* ctx, void* hip_stream, const float* d_xyz, float in_scale, const float* d_precision,
+                         const float* d_box, const float* d_time, const int32_t* d_step, int64_t n_frames, int64_t n_atoms, void* d_image,
+                         uint64_t image_capacity, uint64_t* d_offsets, int32_t* d_status, void* d_work, uint64_t work_bytes);
+
 #ifdef __cplusplus
 }
 #endif

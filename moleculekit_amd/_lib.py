@@ -44,6 +44,10 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _vp, _vp, _vp]),
     "mkamd_xtc_decode_work_bytes": (ctypes.c_uint64, [ctypes.c_int64, ctypes.c_int64]),
     "mkamd_xtc_decode_dev": (_c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, ctypes.c_uint64]),
+    "mkamd_xtc_encode_work_bytes": (ctypes.c_uint64, [ctypes.c_int64, ctypes.c_int64]),
+    "mkamd_xtc_encode_bound": (ctypes.c_uint64, [ctypes.c_int64, ctypes.c_int64]),
+    "mkamd_xtc_encode_dev": (_c_int, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_uint64,
+                                      _vp, _vp, _vp, ctypes.c_uint64]),
     "mkamd_ctx_set_lds_tier": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_prepass_mode": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_pipelining": (_c_int, [_vp, _c_int]),

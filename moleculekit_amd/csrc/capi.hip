@@ -25,6 +25,7 @@
 #include "arith_probe.h"
 #include "host_pack.h"
 #include "xtc_gpu.h"
+#include "xtc_encode.h"
 #include "xtc_headers.h"
 #include "cpu_occupancy.h"
 
@@ -2045,6 +2046,55 @@ try {
         HIP_TRY(hipGetLastError());
     }
     return MKAMD_OK;
+} MK_API_CATCH
+
+// ---- XTC compression on the device (xtc_encode.h): the reference writer's bytes; asynchronous on the caller's stream ----
+namespace {
+struct XtcEncodeStreamBackend {
+    hipStream_t stream;
+    int fill(void* p, int byte, size_t bytes)
+    {
+        HIP_TRY(hipMemsetAsync(p, byte, bytes, stream));
+        return 0;
+    }
+    template <class... KA, class... A>
+    int launch(void (*kernel)(KA...), dim3 grid, dim3 block, A... args)
+    {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+}  // namespace
+
+extern "C" uint64_t mkamd_xtc_encode_work_bytes(int64_t n_frames, int64_t n_atoms) { return mkamd::xtc_encode_layout(n_frames, n_atoms).total; }
+
+extern "C" uint64_t mkamd_xtc_encode_bound(int64_t n_frames, int64_t n_atoms) { return mkamd::xtc_encode_bound(n_frames, n_atoms); }
+
+extern "C" int mkamd_xtc_encode_dev(mkamd_ctx* ctx, void* hip_stream, const float* d_xyz, float in_scale, const float* d_precision,
+                                    const float* d_box, const float* d_time, const int32_t* d_step, int64_t n_frames, int64_t n_atoms,
+                                    void* d_image, uint64_t image_capacity, uint64_t* d_offsets, int32_t* d_status, void* d_work,
+                                    uint64_t work_bytes)
+try {
+    int st = check_ctx(ctx, true);
+    if (st) return st;
+    if (n_frames < 0 || n_atoms < 0) return fail(MKAMD_EINVAL, "n_frames / n_atoms must be >= 0");
+    if (n_frames == 0) return MKAMD_OK;
+    if (n_atoms > 0x7fffffffll) return fail(MKAMD_EINVAL, "an XTC record counts its atoms in an int");
+    if (!d_xyz || !d_precision || !d_box || !d_time || !d_step || !d_image || !d_offsets || !d_status || !d_work) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (work_bytes < mkamd_xtc_encode_work_bytes(n_frames, n_atoms))
+        return fail(MKAMD_EINVAL, "work buffer smaller than mkamd_xtc_encode_work_bytes(n_frames, n_atoms)");
+    if (image_capacity < mkamd_xtc_encode_bound(n_frames, n_atoms))
+        return fail(MKAMD_EINVAL, "image buffer smaller than mkamd_xtc_encode_bound(n_frames, n_atoms)");
+    if (((uintptr_t)d_work & 7u) || ((uintptr_t)d_image & 3u) || ((uintptr_t)d_offsets & 7u))
+        return fail(MKAMD_EINVAL, "d_work and d_offsets must be 8-byte, d_image 4-byte aligned");
+    XtcEncodeStreamBackend be{(hipStream_t)hip_stream};
+    mkamd::XtcEncodeArgs a;
+    a.xyz = d_xyz; a.in_scale = in_scale; a.precision = d_precision; a.box = d_box; a.time = d_time; a.step = d_step;
+    a.n_frames = n_frames; a.n_atoms = n_atoms;
+    a.image = static_cast<unsigned char*>(d_image); a.offsets = reinterpret_cast<unsigned long long*>(d_offsets); a.status = d_status;
+    a.work = static_cast<unsigned char*>(d_work);
+    return mkamd::run_xtc_encode(be, a);
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------

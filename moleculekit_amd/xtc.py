@@ -286,3 +286,204 @@ def write_xtc(filename, coords, box, time, step, precision: float = 1000.0):
             fh.write(head + struct.pack(">i", _FIRSTIDX))                # smallidx: any valid index (never used: no small atoms)
             fh.write(struct.pack(">i", len(payload)))
             fh.write(payload.tobytes() + b"\0" * ((4 - len(payload) % 4) % 4))
+
+
+# ------------------------------------------------------------------------------------------------
+# writing ON THE DEVICE (include/mkamd_xtc.h, csrc/xtc_encode.h): the reference writer's compressed bytes
+# ------------------------------------------------------------------------------------------------
+_REFUSED = ("is outside what the device writer takes: a coordinate that is not finite or leaves the int range at this precision, a "
+            "coordinate range of >= 2^31 quanta, a full coordinate of more than 64 bits (ranges beyond ~2 million quanta per axis), a "
+            "smallest neighbour step so large that the small-number index of the header exceeds 56, or >= 2^21 atoms")
+
+
+def _to_dev(v, dtype, dev, shape=None):
+    import torch
+    if isinstance(v, torch.Tensor):
+        t = v.to(device=dev, dtype=dtype)
+        return (t.expand(shape) if t.ndim == 0 else t.reshape(shape)).contiguous()
+    a = np.asarray(v, dtype={torch.float32: np.float32, torch.int32: np.int32}[dtype])
+    a = np.array(np.broadcast_to(a, shape) if a.ndim == 0 else a.reshape(shape))       # (a writable copy: torch asks for one)
+    return torch.as_tensor(a).to(dev)
+
+
+def _step_i32(step):
+    """Steps as the 32 bits an XTC record holds (the reference hands them over as unsigned)."""
+    import torch
+    if isinstance(step, torch.Tensor):
+        return step
+    return (np.asarray(step).astype(np.int64) & 0xffffffff).astype(np.uint32).view(np.int32)
+
+
+def encode_xtc_dev(xyz, box, time, step, precision=1000.0, scale: float = 1.0, ctx=None):
+    """The XTC file image of frames resident on the GPU, byte for byte what the reference's writer makes of them.
+
+    ``xyz`` float32 CUDA tensor ``[F, N, 3]`` (frame-major, as ``read_xtc_frames_dev`` returns it), ``box`` the box vectors
+    ``[3, 3, F]`` in nm, ``time`` ``[F]`` in ps, ``step`` ``[F]`` (arrays or tensors, as that reader returns them), ``precision`` a
+    scalar or one value per frame; every coordinate is multiplied by ``scale`` first, rounded to float32 once (1 for nm, the float32
+    0.1 for Angstrom).  Returns ``(image, offsets, status)``: a uint8 CUDA tensor trimmed to the records' total size, the records'
+    byte offsets (int64 numpy ``[F + 1]``) and per frame 0 or 2 (int32 numpy ``[F]``); a frame of status 2 is outside what the device
+    path takes and has no bytes in the image -- nothing falls back to another encoder."""
+    import torch
+
+    ctx = ctx or _lib.default_context()
+    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda or xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be a CUDA tensor of shape (nframes, natoms, 3)")
+    dev = xyz.device
+    F, N = int(xyz.shape[0]), int(xyz.shape[1])
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        x = xyz.to(torch.float32).contiguous()
+        b = box if isinstance(box, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(box, np.float32))
+        if tuple(b.shape) != (3, 3, F):
+            raise ValueError("box must hold one set of box vectors per frame: (3, 3, nframes)")
+        d_box = b.to(device=dev, dtype=torch.float32).permute(2, 0, 1).contiguous()
+        d_time = _to_dev(time, torch.float32, dev, (F,))
+        d_step = _to_dev(_step_i32(step), torch.int32, dev, (F,))
+        d_prec = _to_dev(precision, torch.float32, dev, (F,))
+        bound = int(lib.mkamd_xtc_encode_bound(F, N))
+        image = torch.empty(max(bound, 4), dtype=torch.uint8, device=dev)
+        d_off = torch.zeros(F + 1, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(F, dtype=torch.int32, device=dev)
+        work = torch.empty(max(int(lib.mkamd_xtc_encode_work_bytes(F, N)), 8), dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev)
+        _lib._check(lib.mkamd_xtc_encode_dev(ctx._h, s.cuda_stream or None, x.data_ptr(), float(np.float32(scale)), d_prec.data_ptr(),
+                                             d_box.data_ptr(), d_time.data_ptr(), d_step.data_ptr(), F, N, image.data_ptr(), bound,
+                                             d_off.data_ptr(), d_st.data_ptr(), work.data_ptr(), work.numel()))
+        offsets = d_off.cpu().numpy()
+        status = d_st.cpu().numpy()
+    return image[:int(offsets[-1])], offsets, status
+
+
+def _index_side_file(filename):
+    """The frame-index side file an installed moleculekit keeps beside a trajectory (``<dir>/.<name>``); this package's own reader
+    keeps its index in memory, keyed by the file's identity, and needs no invalidation."""
+    import os
+    d, name = os.path.split(os.fspath(filename))
+    return os.path.join(d, "." + name)
+
+
+def default_chunk(natoms: int) -> int:
+    """Frames ``write_xtc_dev`` encodes per call unless told otherwise: work buffer and image (24 + 13 bytes per atom) of about
+    4 GiB.  A call's time is the longest frame's walk whatever the number of frames, so fewer, larger chunks are faster."""
+    return max(1, (4 << 30) // (40 * int(natoms) + 256))
+
+
+def write_xtc_dev(filename, xyz, box, time, step, precision=1000.0, scale: float = 1.0, append: bool = False, chunk=None, ctx=None):
+    """Write frames resident on the GPU as an XTC file with the reference writer's bytes (arguments as ``encode_xtc_dev``).
+
+    Chunks of ``chunk`` frames are encoded on the device and copied out through pinned memory into a temporary file next to the
+    target; on success it is renamed over the target, or its bytes are appended with ``append=True``.  If a frame is outside what the
+    device path takes, ``RuntimeError`` names the first one and the target is left as it was."""
+    import os
+    import torch
+
+    if not isinstance(xyz, torch.Tensor) or xyz.ndim != 3:
+        raise ValueError("xyz must be a CUDA tensor of shape (nframes, natoms, 3)")
+    F, N = int(xyz.shape[0]), int(xyz.shape[1])
+    fn = os.fspath(filename)
+    fn = fn.decode("UTF-8") if isinstance(fn, bytes) else fn
+    chunk = default_chunk(N) if chunk is None else max(1, int(chunk))
+    b = box if isinstance(box, torch.Tensor) else np.ascontiguousarray(box, np.float32)
+    per = lambda v, lo, hi: v if getattr(v, "ndim", 0) == 0 else v[lo:hi]   # noqa: E731
+    tmp = "%s.tmp.%d" % (fn, os.getpid())
+    try:
+        with open(tmp, "wb") as fh:
+            for lo in range(0, F, chunk):
+                hi = min(F, lo + chunk)
+                image, _, status = encode_xtc_dev(xyz[lo:hi], b[:, :, lo:hi], per(time, lo, hi), per(step, lo, hi), per(precision, lo, hi),
+                                                  scale, ctx)
+                if status.any():
+                    raise RuntimeError(f"device XTC writer: frame {lo + int(np.flatnonzero(status)[0])} {_REFUSED}")
+                if image.numel():
+                    host = torch.empty(image.numel(), dtype=torch.uint8, pin_memory=True)
+                    host.copy_(image, non_blocking=True)
+                    torch.cuda.current_stream(image.device).synchronize()
+                    fh.write(memoryview(host.numpy()))
+        side = _index_side_file(fn)
+        if os.path.isfile(side):
+            os.remove(side)
+        if append and os.path.exists(fn):
+            with open(fn, "ab") as out, open(tmp, "rb") as src:
+                while True:
+                    buf = src.read(1 << 24)
+                    if not buf:
+                        break
+                    out.write(buf)
+        else:
+            os.replace(tmp, fn)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def _xtcwrite_arrays(mol):
+    """What ``writers.XTCwrite`` (writers.py:271-311) hands to its writer, from a duck-typed molecule: ``(coords float32 [N, 3, F] in
+    Angstrom, box vectors float32 [3, 3, F] in nm, time float32 [F] in ps, step uint32 [F])``.  Box vectors default to zeros and one
+    frame's are repeated for every frame; steps that do not fit 32 bits are renumbered from 1; times (fs) that float32 cannot hold are
+    rebuilt from ``fstep`` and the step stride, starting from the first frame (``_format_large_time``)."""
+    coords = np.asarray(mol.coords)
+    nframes = int(getattr(mol, "numFrames", coords.shape[2]))
+    box = np.zeros((3, 3, nframes), dtype=np.float32)
+    if hasattr(mol, "box") and getattr(mol, "boxvectors", None) is not None:
+        box = np.asarray(mol.boxvectors)
+    if np.size(box, 2) != nframes:
+        box = np.tile(box, (1, 1, nframes))
+    step = np.asarray(getattr(mol, "step", np.zeros(nframes, dtype=np.int64)))
+    time = np.asarray(getattr(mol, "time", np.zeros(nframes)))
+    trajfreq = step[0] if len(step) == 1 else step[1] - step[0]
+    if step[-1] != step[-1].astype(np.uint32):
+        out_step = np.arange(1, nframes + 1, dtype=np.uint32)
+    else:
+        out_step = step.astype(np.uint32)
+    out_time = time / 1e3                                            # fs -> ps
+    if out_time[-1] != out_time[-1].astype(np.float32):
+        if trajfreq == 0:
+            raise AssertionError("The trajectory step should not be 0")
+        timestep = (mol.fstep / trajfreq) / 1e-6
+        out_time = (time - ((step[0] - trajfreq) * timestep)) / 1e3
+    return coords, np.ascontiguousarray(box.astype(np.float32) * 0.1), np.ascontiguousarray(out_time.astype(np.float32)), np.ascontiguousarray(out_step)
+
+
+def XTCwrite(mol, filename, ctx=None):
+    """``writers.XTCwrite`` with the compression on the GPU: the same file, byte for byte.  Precision 1000; coordinates go to nm as
+    float32 ``* 0.1`` on the device; an existing file is replaced.  Only the coordinates, box vectors, times and steps travel to the
+    device."""
+    import torch
+
+    ctx = ctx or _lib.default_context()
+    coords, box, time, step = _xtcwrite_arrays(mol)
+    dev = torch.device("cuda", ctx.device)
+    xyz = torch.as_tensor(np.ascontiguousarray(np.asarray(coords, dtype=np.float32).transpose(2, 0, 1))).to(dev)
+    write_xtc_dev(filename, xyz, box, time, step, precision=1000.0, scale=float(np.float32(0.1)), ctx=ctx)
+
+
+def install():
+    """Make an installed moleculekit write XTC files through the GPU: swaps ``moleculekit.writers.XTCwrite`` and the ``"xtc"`` entry of
+    ``moleculekit.writers._WRITERS``.  Returns the original function; ``uninstall()`` puts both back."""
+    import moleculekit.writers as ref
+
+    if getattr(ref, "_XTCwrite_reference", None) is not None:           # already installed
+        return ref._XTCwrite_reference
+    original = ref.XTCwrite
+    hook = lambda mol, filename, **kw: XTCwrite(mol, filename, **kw)   # noqa: E731
+    ref._XTCwrite_reference = original
+    ref._WRITERS_xtc_reference = ref._WRITERS.get("xtc")
+    ref.XTCwrite = hook
+    ref._WRITERS["xtc"] = hook
+    return original
+
+
+def uninstall():
+    """Undo ``install()``."""
+    import moleculekit.writers as ref
+
+    original = getattr(ref, "_XTCwrite_reference", None)
+    if original is None:
+        return
+    ref.XTCwrite = original
+    if ref._WRITERS_xtc_reference is not None:
+        ref._WRITERS["xtc"] = ref._WRITERS_xtc_reference
+    else:
+        ref._WRITERS.pop("xtc", None)
+    ref._XTCwrite_reference = None
+    ref._WRITERS_xtc_reference = None
