@@ -86,6 +86,56 @@ int mkamd_xtc_encode_dev(struct mkamd_ctx* ctx, void* hip_stream, const float* d
                          const float* d_box, const float* d_time, const int32_t* d_step, int64_t n_frames, int64_t n_atoms, void* d_image,
                          uint64_t image_capacity, uint64_t* d_offsets, int32_t* d_status, void* d_work, uint64_t work_bytes);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * DCD (CHARMM / NAMD / X-PLOR / OpenMM trajectories; csrc/dcd_reader.h, csrc/dcd_kernels.h).  What the reference does in
+ * moleculekit/fileformats/dcd (src/dcdplugin.c, dcd.pyx): coordinates are float32 bit patterns carried unchanged, Angstrom.
+ * A frame is three planes of floats at offsets the header fixes; the host parses the header and checks every selected frame's
+ * markers, the device gathers, byte-swaps and transposes.
+ *   mkamd_dcd_info          atom count, frame count (from the file's size: a frame cut off at the end is not counted), ISTART, NSAVC,
+ *                           DELTA, the number of fixed atoms and flags (1 opposite endian, 2 64-bit record markers, 4 CHARMM, 8 unit
+ *                           cells, 16 a 4th dimension).  Refused with a message: opposite endian with a 4th dimension (the reference
+ *                           misreads it), N <= 0, fixed atoms outside [0, N), free indices outside 1..N or not strictly ascending.
+ *   mkamd_dcd_chunk_desc    the selected frames (any order, repeats allowed; NULL = 0 .. n_sel-1) -> one 32-byte descriptor each
+ *                           (mkamd::dcd::FrameDesc: byte offsets of the x, y, z planes counted from *byte_lo, floats per plane, flags:
+ *                           1 swap, 2 free atoms only), the byte range [*byte_lo, *byte_hi) that holds them (a multiple of 4, copy it
+ *                           with mkamd_xtc_copy_bytes) and the unit cells f32 [n_sel, 6]: A, B, C, alpha, beta, gamma (degrees; from
+ *                           the stored cosines when all three lie in [-1, 1]; 0 0 0 90 90 90 in a file without cells).  Every marker
+ *                           of a selected frame is checked against N, every descriptor against the file's size.
+ *   mkamd_dcd_source_table  the atom selection (NULL = all n_sel = N atoms) composed with the fixed-atom map: sel i32 [n_sel] the checked
+ *                           indices (into a full frame's planes), src i32 [n_sel] for a frame of free atoms only: >= 0 an index into its
+ *                           planes, < 0 atom -1 - src of frame 0
+ *   mkamd_dcd_read          the host path: selected frames and atoms into xyz f32 [n_frames, n_sel, 3], cells f32 [n_frames, 6]
+ *   mkamd_dcd_decode_dev    (needs mkamd_voxel.h's context) d_bytes = device copy of the byte range (4-byte aligned, n_bytes long),
+ *                           d_desc / d_sel / d_src device copies of the above, d_frame0 f32 [n_atoms, 3] = frame 0 decoded with the
+ *                           identity selection and scale 1 (NULL for a file without fixed atoms) -> d_xyz f32 [n_frames, n_sel, 3]
+ *                           times `scale` (multiplied only when != 1), d_status i32 [n_frames]: 0 ok, 1 a descriptor that reaches
+ *                           outside n_bytes or is misaligned (nothing of that frame is stored) or a table entry outside its plane (that
+ *                           item is not stored).  Asynchronous on `hip_stream`.
+ *   mkamd_dcd_encode_bound  bytes of the image of n_frames frames: (with_cell ? 56 : 0) + 3 * (4 * n_atoms + 8) each
+ *   mkamd_dcd_encode_dev    d_xyz f32 [n_frames, n_atoms, 3] -> the reference writer's frame images one after the other in d_image
+ *                           (4-byte aligned); d_cell f64 [n_frames, 6] = the six doubles of each frame's cell record (mkamd_dcd_cell_record),
+ *                           or NULL for a file without unit cells.  Every byte is written exactly once.  Asynchronous on `hip_stream`.
+ *   mkamd_dcd_cell_record   lengths / angles f32 [n, 3] (degrees) -> the cell records f64 [n, 6]: A, cos(gamma), B, cos(beta), cos(alpha), C
+ *                           with the cosines as sin(pi/2 / 90 * (90 - angle)), like the reference's writer
+ *   mkamd_dcd_header        the 276-byte file header of that writer with NSET = n_frames (byte 8) and ISTART + n_frames * NSAVC (byte 20)
+ *                           in place; bytes [180, 260) are "REMARKS Created <asctime>", zero-padded. */
+#define MKAMD_DCD_DESC_BYTES 32
+#define MKAMD_DCD_HEADER_BYTES 276
+int mkamd_dcd_info(const char* path, int64_t* n_atoms, int64_t* n_frames, int32_t* istart, int32_t* nsavc, double* delta, int32_t* n_fixed,
+                   int32_t* flags);
+int mkamd_dcd_chunk_desc(const char* path, const int64_t* frames, int64_t n_sel, void* desc_out, int64_t* byte_lo, int64_t* byte_hi,
+                         float* cell);
+int mkamd_dcd_source_table(const char* path, const int32_t* atoms, int64_t n_sel, int32_t* sel, int32_t* src);
+int mkamd_dcd_read(const char* path, const int64_t* frames, int64_t n_frames, const int32_t* atoms, int64_t n_sel, float* xyz, float* cell);
+int mkamd_dcd_decode_dev(struct mkamd_ctx* ctx, void* hip_stream, const void* d_bytes, uint64_t n_bytes, const void* d_desc, int64_t n_frames,
+                         const int32_t* d_sel, const int32_t* d_src, int64_t n_sel, const float* d_frame0, int64_t n_atoms, float scale,
+                         float* d_xyz, int32_t* d_status);
+uint64_t mkamd_dcd_encode_bound(int64_t n_frames, int64_t n_atoms, int32_t with_cell);
+int mkamd_dcd_encode_dev(struct mkamd_ctx* ctx, void* hip_stream, const float* d_xyz, const double* d_cell, int64_t n_frames, int64_t n_atoms,
+                         void* d_image, uint64_t image_capacity);
+int mkamd_dcd_cell_record(const float* lengths, const float* angles, int64_t n, double* out);
+int mkamd_dcd_header(int64_t n_atoms, int64_t n_frames, int32_t istart, int32_t nsavc, double delta, int32_t with_cell, void* out);
+
 #ifdef __cplusplus
 }
 #endif

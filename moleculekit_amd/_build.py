@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libmkamd.so")
 HOST_LIB = os.path.join(CSRC, "libmkamd_host.so")          # the host entry point alone, plain C++ (no ROCm): build_host()
-SOURCES = ["capi.hip", "pipeline.h", "kernels.h", "mk_device.h", "mk_diagnostics.h", "dist_kernels.h", "dist_pipeline.h", "xtc_reader.h", "xtc_gpu.h", "xtc_encode.h", "cpu_occupancy.h", "host_pack.h", "mk_affine.h", "align_kernels.h", "align_pipeline.h", "sasa_kernels.h", "sasa_pipeline.h", "shell_kernels.h", "shell_pipeline.h", "dihedral_kernels.h", "dihedral_pipeline.h", "moments_kernels.h", "moments_pipeline.h", "wrap_kernels.h", "wrap_pipeline.h", "wrap_cell_kernels.h", "wrap_cell_pipeline.h", "ring_kernels.h", "ring_pipeline.h", "hbond_kernels.h", "hbond_pipeline.h", "arith_probe.h", "bond_kernels.h", "bond_pipeline.h", "clash_kernels.h", "clash_pipeline.h", "within_kernels.h", "within_pipeline.h", "dssp_kernels.h", "dssp_pipeline.h"]
+SOURCES = ["capi.hip", "pipeline.h", "kernels.h", "mk_device.h", "mk_diagnostics.h", "dist_kernels.h", "dist_pipeline.h", "xtc_reader.h", "xtc_gpu.h", "xtc_encode.h", "dcd_reader.h", "dcd_kernels.h", "cpu_occupancy.h", "host_pack.h", "mk_affine.h", "align_kernels.h", "align_pipeline.h", "sasa_kernels.h", "sasa_pipeline.h", "shell_kernels.h", "shell_pipeline.h", "dihedral_kernels.h", "dihedral_pipeline.h", "moments_kernels.h", "moments_pipeline.h", "wrap_kernels.h", "wrap_pipeline.h", "wrap_cell_kernels.h", "wrap_cell_pipeline.h", "ring_kernels.h", "ring_pipeline.h", "hbond_kernels.h", "hbond_pipeline.h", "arith_probe.h", "bond_kernels.h", "bond_pipeline.h", "clash_kernels.h", "clash_pipeline.h", "within_kernels.h", "within_pipeline.h", "dssp_kernels.h", "dssp_pipeline.h"]
 HEADER = os.path.join(_HERE, "..", "include", "mkamd_voxel.h")
 HEADER2 = os.path.join(_HERE, "..", "include", "mkamd_distance.h")
 HEADER3 = os.path.join(_HERE, "..", "include", "mkamd_xtc.h")

@@ -48,6 +48,17 @@ SIGNATURES = {
     "mkamd_xtc_encode_bound": (ctypes.c_uint64, [ctypes.c_int64, ctypes.c_int64]),
     "mkamd_xtc_encode_dev": (_c_int, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_uint64,
                                       _vp, _vp, _vp, ctypes.c_uint64]),
+    "mkamd_dcd_info": (_c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_c_i32),
+                                ctypes.POINTER(_c_i32), ctypes.POINTER(_c_dbl), ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32)]),
+    "mkamd_dcd_chunk_desc": (_c_int, [ctypes.c_char_p, _vp, ctypes.c_int64, _vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _vp]),
+    "mkamd_dcd_source_table": (_c_int, [ctypes.c_char_p, _vp, ctypes.c_int64, _vp, _vp]),
+    "mkamd_dcd_read": (_c_int, [ctypes.c_char_p, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp]),
+    "mkamd_dcd_decode_dev": (_c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64,
+                                      ctypes.c_float, _vp, _vp]),
+    "mkamd_dcd_encode_bound": (ctypes.c_uint64, [ctypes.c_int64, ctypes.c_int64, _c_i32]),
+    "mkamd_dcd_encode_dev": (_c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_uint64]),
+    "mkamd_dcd_cell_record": (_c_int, [_vp, _vp, ctypes.c_int64, _vp]),
+    "mkamd_dcd_header": (_c_int, [ctypes.c_int64, ctypes.c_int64, _c_i32, _c_i32, _c_dbl, _c_i32, _vp]),
     "mkamd_ctx_set_lds_tier": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_prepass_mode": (_c_int, [_vp, _c_int]),
     "mkamd_ctx_set_pipelining": (_c_int, [_vp, _c_int]),

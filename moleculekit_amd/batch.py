@@ -822,3 +822,111 @@ def _iter_xtc_gpu(filename, path, natoms, fr, box_lengths, nvoxels, has_box, cha
         for i in range(2):
             if h_raw[i] is not None:
                 _pinned_give(("xtcraw", i), h_raw[i])
+
+
+def iterVoxelizeDCD(filename, channels, center, boxsize, voxelsize=1, pbc=True, frames=None, atom_indices=None, chunk=1024, device=None,
+                    channel_first=False, ctx=None, pipelined=True, decode="gpu", ramp=0, align=None):
+    """``iterVoxelizeTrajectory`` fed straight from a DCD file (Angstrom: no unit conversion).  ``pbc``: use the frames' cell lengths
+    for the minimum image, as ``iterVoxelizeXTC`` uses the lengths of the box vectors.  ``atom_indices``: voxelize these atoms only
+    (``channels`` then has one row per selected atom).
+
+    ``decode``: where a chunk's frames become frame-major items --
+      ``"gpu"``   on the device (csrc/dcd_kernels.h): per chunk the host checks the frames' record markers, copies the bytes between
+                  the chunk's lowest and highest frame into one of two pinned buffers and uploads them; a kernel gathers, byte-swaps
+                  and transposes the planes straight into the voxelizer's items.  Any frame list is taken; a sparse one uploads
+                  the whole span.
+      ``"host"``  by the host loop of ``moleculekit_amd.dcd`` (``mkamd_dcd_read``) into pinned staging.
+    A frame whose descriptor the kernel refuses raises before its chunk's features are handed out; the host has checked every
+    descriptor against the file before, so that only guards against a file that changed in between.
+
+    ``align = (ref_xyz [n, 3] Angstrom, sel)``: as ``iterVoxelizeTrajectory``'s (needs ``pbc=False``)."""
+    if align is not None and pbc:
+        raise ValueError("align needs pbc=False (the minimum image is axis-aligned; a rotation breaks it)")
+    if decode not in ("gpu", "host"):
+        raise ValueError('decode must be "gpu" or "host"')
+
+    from . import dcd as _dcd
+    head = _dcd.info(filename)
+    natoms, nframes = head["n_atoms"], head["n_frames"]
+    atoms = _dcd._atoms(atom_indices, natoms)
+    nsel = natoms if atoms is None else len(atoms)
+    fr = np.arange(nframes, dtype=np.int64) if frames is None else np.asarray(frames, dtype=np.int64)
+    lib, path = _lib.load(), _dcd._path(filename)
+    max_images = 1
+    nvoxels = np.ceil(np.array(boxsize, dtype=np.float64) / voxelsize).astype(int)
+    if pbc and len(fr):
+        lengths = _dcd.chunk_desc(filename, fr[:1])[3][0, :3].astype(np.float64)     # first guess; every chunk recomputes it
+        if not np.all(lengths > 0):
+            raise ValueError("pbc=True but the DCD frames carry no unit cell")
+        max_images = max_images_per_atom(lengths[None, :] * 0.98, nvoxels, voxelsize)
+
+    if decode == "host" or not len(fr):
+        def fill(dst, dst_box, idx):
+            n = len(idx)
+            sel = np.ascontiguousarray(idx, dtype=np.int64)
+            xyz = np.empty((n, nsel, 3), dtype=np.float32)
+            cell = np.empty((n, 6), dtype=np.float32)
+            _lib._check(lib.mkamd_dcd_read(path, _lib._ptr(sel), n, _lib._ptr(atoms), nsel, _lib._ptr(xyz), _lib._ptr(cell)))
+            np.copyto(dst, xyz.transpose(1, 2, 0))
+            if dst_box is not None:
+                np.copyto(dst_box, cell[:, :3].T)
+
+        yield from _stream_voxelize(nsel, fr, fill, 1.0, bool(pbc), channels, center, boxsize, voxelsize, chunk, device, channel_first,
+                                    ctx, max_images, pipelined=pipelined, ramp=ramp, align=align)
+        return
+
+    import torch
+
+    run_ctx = ctx or _lib.default_context(None if device is None else torch.device(device).index)
+    rd = _dcd.DeviceReader(filename, atoms, run_ctx)
+    dev = rd.dev
+    has_box = bool(pbc)
+    h_raw, d_raw = [None, None], [None, None]                     # two slots of byte buffers, grown as chunks need them
+    up = [torch.cuda.Event(), torch.cuda.Event()]                 # the upload out of h_raw[slot] is done
+    statuses = []                                                 # (event, pinned statuses, frame indices) of the chunks in flight
+    state = {"k": 0}
+
+    def fill_dev(copy, xyz, bx, idx):                             # inside the copy-stream context of _stream_voxelize
+        k = state["k"]
+        state["k"] += 1
+        slot = k & 1
+        up[slot].synchronize()                                    # chunk k-2's upload: h_raw[slot] may be overwritten
+        n = len(idx)
+        h_raw[slot], nb, desc, cell = rd.stage(np.ascontiguousarray(idx, dtype=np.int64), h_raw[slot])
+        if d_raw[slot] is None or d_raw[slot].numel() < nb:
+            d_raw[slot] = torch.empty(int(nb * 1.25) + 4096, dtype=torch.uint8, device=dev)   # (stream-ordered: the decode of chunk
+        d_bytes = d_raw[slot][:nb]                                #  k-2 that read the old one was enqueued on this stream)
+        d_bytes.copy_(h_raw[slot][:nb], non_blocking=True)
+        up[slot].record(copy)
+        d_desc = torch.as_tensor(desc).pin_memory().to(dev, non_blocking=True)
+        d_st = torch.empty(n, dtype=torch.int32, device=dev)
+        rd.launch(d_bytes, d_desc, n, xyz, d_st, 1.0, stream=copy.cuda_stream)
+        h_st = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        h_st.copy_(d_st, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(copy)
+        statuses.append((done, h_st, np.array(idx, copy=True)))
+        images = max_images
+        if has_box:
+            hb = np.ascontiguousarray(cell[:, :3].T)              # [3, n]
+            bx.copy_(torch.as_tensor(np.ascontiguousarray(cell[:, :3])).pin_memory(), non_blocking=True)
+            images = max(max_images, _chunk_images(hb, nvoxels, voxelsize))
+        return images
+
+    def check():                                                  # the oldest chunk not looked at yet: its decode is waited for
+        done, h_st, idx = statuses.pop(0)
+        done.synchronize()
+        st = h_st.numpy()
+        if st.any():
+            raise RuntimeError(f"{filename}: frame {int(idx[int(np.flatnonzero(st)[0])])} reaches outside the bytes the device decoder was given")
+
+    gen = _stream_voxelize(nsel, fr, None, 1.0, has_box, channels, center, boxsize, voxelsize, chunk, device, channel_first, run_ctx,
+                           max_images, fill_dev=fill_dev, pipelined=pipelined, ramp=ramp, align=align)
+    # A chunk's features are handed out only once ITS statuses were read and are all 0: a refused frame's items are whatever the slot held
+    # before.  The wait is short -- the chunk's voxelization, already enqueued, waits for the same decode.
+    try:
+        for item in gen:
+            check()
+            yield item
+    finally:
+        gen.close()

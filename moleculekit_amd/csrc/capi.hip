@@ -26,6 +26,7 @@
 #include "host_pack.h"
 #include "xtc_gpu.h"
 #include "xtc_encode.h"
+#include "dcd_kernels.h"
 #include "xtc_headers.h"
 #include "cpu_occupancy.h"
 
@@ -2095,6 +2096,127 @@ try {
     a.image = static_cast<unsigned char*>(d_image); a.offsets = reinterpret_cast<unsigned long long*>(d_offsets); a.status = d_status;
     a.work = static_cast<unsigned char*>(d_work);
     return mkamd::run_xtc_encode(be, a);
+} MK_API_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// DCD (include/mkamd_xtc.h "DCD"; dcd_reader.h on the host, dcd_kernels.h on the device)
+// ---------------------------------------------------------------------------------------------
+extern "C" int mkamd_dcd_info(const char* path, int64_t* n_atoms, int64_t* n_frames, int32_t* istart, int32_t* nsavc, double* delta,
+                              int32_t* n_fixed, int32_t* flags)
+try {
+    if (!path || !n_atoms || !n_frames) return fail(MKAMD_EINVAL, "path/n_atoms/n_frames pointer is NULL");
+    mkamd::xtc::Mapped m;
+    mkamd::dcd::Header h;
+    std::string err;
+    if (mkamd::dcd::open_header(path, m, h, err)) return fail(MKAMD_EINVAL, err);
+    *n_atoms = h.n_atoms; *n_frames = h.n_frames;
+    if (istart) *istart = h.istart;
+    if (nsavc) *nsavc = h.nsavc;
+    if (delta) *delta = h.delta;
+    if (n_fixed) *n_fixed = h.nfixed;
+    if (flags) *flags = h.flags;
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_dcd_chunk_desc(const char* path, const int64_t* frames, int64_t n_sel, void* desc_out, int64_t* byte_lo, int64_t* byte_hi,
+                                    float* cell)
+try {
+    if (!path || !desc_out || !byte_lo || !byte_hi || !cell) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (n_sel <= 0) return fail(MKAMD_EINVAL, "n_sel must be > 0");
+    mkamd::xtc::Mapped m;
+    mkamd::dcd::Header h;
+    std::string err;
+    if (mkamd::dcd::open_header(path, m, h, err)) return fail(MKAMD_EINVAL, err);
+    if (mkamd::dcd::chunk_desc(m.p, m.n, h, frames, n_sel, static_cast<mkamd::dcd::FrameDesc*>(desc_out), byte_lo, byte_hi, cell, err))
+        return fail(MKAMD_EINVAL, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_dcd_source_table(const char* path, const int32_t* atoms, int64_t n_sel, int32_t* sel, int32_t* src)
+try {
+    if (!path) return fail(MKAMD_EINVAL, "path is NULL");
+    if (n_sel < 0) return fail(MKAMD_EINVAL, "n_sel must be >= 0");
+    if (n_sel == 0) return MKAMD_OK;
+    if (!sel || !src) return fail(MKAMD_EINVAL, "NULL pointer");
+    mkamd::xtc::Mapped m;
+    mkamd::dcd::Header h;
+    std::string err;
+    if (mkamd::dcd::open_header(path, m, h, err)) return fail(MKAMD_EINVAL, err);
+    if (!atoms && n_sel != h.n_atoms) return fail(MKAMD_EINVAL, "without an atom list n_sel must be the file's atom count");
+    if (mkamd::dcd::source_table(h, atoms, n_sel, sel, src, err)) return fail(MKAMD_EINVAL, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_dcd_read(const char* path, const int64_t* frames, int64_t n_frames, const int32_t* atoms, int64_t n_sel, float* xyz,
+                              float* cell)
+try {
+    if (!path) return fail(MKAMD_EINVAL, "path is NULL");
+    if (n_frames < 0 || n_sel < 0) return fail(MKAMD_EINVAL, "n_frames and n_sel must be >= 0");
+    if (n_frames == 0) return MKAMD_OK;
+    if (!cell || (n_sel > 0 && !xyz)) return fail(MKAMD_EINVAL, "xyz/cell pointer is NULL");
+    mkamd::xtc::Mapped m;
+    mkamd::dcd::Header h;
+    std::string err;
+    if (mkamd::dcd::open_header(path, m, h, err)) return fail(MKAMD_EINVAL, err);
+    if (!atoms && n_sel != h.n_atoms) return fail(MKAMD_EINVAL, "without an atom list n_sel must be the file's atom count");
+    if (mkamd::dcd::read(m.p, m.n, h, frames, n_frames, atoms, n_sel, xyz, cell, err)) return fail(MKAMD_EINVAL, err);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_dcd_decode_dev(mkamd_ctx* ctx, void* hip_stream, const void* d_bytes, uint64_t n_bytes, const void* d_desc, int64_t n_frames,
+                                    const int32_t* d_sel, const int32_t* d_src, int64_t n_sel, const float* d_frame0, int64_t n_atoms,
+                                    float scale, float* d_xyz, int32_t* d_status)
+try {
+    int st = check_ctx(ctx, true);
+    if (st) return st;
+    if (n_frames < 0 || n_sel < 0 || n_atoms < 0) return fail(MKAMD_EINVAL, "n_frames / n_sel / n_atoms must be >= 0");
+    if (n_frames == 0) return MKAMD_OK;
+    if (n_atoms > 0x7fffffffll || n_sel > 0x7fffffffll) return fail(MKAMD_EINVAL, "a DCD file counts its atoms in an int");
+    if (!d_bytes || !d_desc || !d_status || (n_sel > 0 && (!d_sel || !d_src || !d_xyz))) return fail(MKAMD_EINVAL, "NULL pointer");
+    if ((uintptr_t)d_bytes & 3u) return fail(MKAMD_EINVAL, "d_bytes must be 4-byte aligned");
+    XtcEncodeStreamBackend be{(hipStream_t)hip_stream};
+    return mkamd::run_dcd_decode(be, static_cast<const unsigned char*>(d_bytes), (unsigned long long)n_bytes,
+                                 static_cast<const mkamd::dcd::FrameDesc*>(d_desc), (long long)n_frames, d_sel, d_src, (long long)n_sel, d_frame0,
+                                 (long long)n_atoms, scale, d_xyz, d_status);
+} MK_API_CATCH
+
+extern "C" uint64_t mkamd_dcd_encode_bound(int64_t n_frames, int64_t n_atoms, int32_t with_cell)
+{
+    if (n_frames <= 0 || n_atoms <= 0) return 0;
+    return (uint64_t)n_frames * mkamd::dcd_frame_bytes(n_atoms, with_cell != 0);
+}
+
+extern "C" int mkamd_dcd_encode_dev(mkamd_ctx* ctx, void* hip_stream, const float* d_xyz, const double* d_cell, int64_t n_frames, int64_t n_atoms,
+                                    void* d_image, uint64_t image_capacity)
+try {
+    int st = check_ctx(ctx, true);
+    if (st) return st;
+    if (n_frames < 0 || n_atoms <= 0) return fail(MKAMD_EINVAL, "n_frames must be >= 0 and n_atoms > 0");
+    if (n_frames == 0) return MKAMD_OK;
+    if (n_atoms >= (1ll << 29)) return fail(MKAMD_EINVAL, "a DCD record marker holds 4 * n_atoms in an int");
+    if (!d_xyz || !d_image) return fail(MKAMD_EINVAL, "NULL pointer");
+    if (image_capacity < mkamd_dcd_encode_bound(n_frames, n_atoms, d_cell != nullptr))
+        return fail(MKAMD_EINVAL, "image buffer smaller than mkamd_dcd_encode_bound(n_frames, n_atoms, with_cell)");
+    if (((uintptr_t)d_image & 3u) || ((uintptr_t)d_cell & 7u)) return fail(MKAMD_EINVAL, "d_image must be 4-byte, d_cell 8-byte aligned");
+    XtcEncodeStreamBackend be{(hipStream_t)hip_stream};
+    return mkamd::run_dcd_encode(be, d_xyz, d_cell, (long long)n_frames, (long long)n_atoms, static_cast<unsigned char*>(d_image));
+} MK_API_CATCH
+
+extern "C" int mkamd_dcd_cell_record(const float* lengths, const float* angles, int64_t n, double* out)
+try {
+    if (n < 0) return fail(MKAMD_EINVAL, "n must be >= 0");
+    if (n > 0 && (!lengths || !angles || !out)) return fail(MKAMD_EINVAL, "NULL pointer");
+    for (int64_t i = 0; i < n; ++i) mkamd::dcd::cell_record(lengths + 3 * i, angles + 3 * i, out + 6 * i);
+    return MKAMD_OK;
+} MK_API_CATCH
+
+extern "C" int mkamd_dcd_header(int64_t n_atoms, int64_t n_frames, int32_t istart, int32_t nsavc, double delta, int32_t with_cell, void* out)
+try {
+    if (!out) return fail(MKAMD_EINVAL, "out is NULL");
+    if (n_atoms <= 0 || n_atoms >= (1ll << 29)) return fail(MKAMD_EINVAL, "n_atoms must be in [1, 2^29)");
+    if (n_frames < 0 || n_frames > 0x7fffffffll) return fail(MKAMD_EINVAL, "n_frames must fit an int");
+    mkamd::dcd::write_header((int32_t)n_atoms, (int32_t)n_frames, istart, nsavc, delta, with_cell != 0, static_cast<uint8_t*>(out));
+    return MKAMD_OK;
 } MK_API_CATCH
 
 // ---------------------------------------------------------------------------------------------
